@@ -11,8 +11,13 @@ each rank its own 256×256 block with a replicated fit instead.
     python bench.py [--gpus N] [--steps K] [--warmup W]   (N > 1: starts the N ranks itself)
     torchrun --nproc-per-node N bench.py --gpus N ...     (--gpus must equal WORLD_SIZE)
 
-Rank 0 prints ONE JSON line (the driver contract) with `roofline` (dominant
-kernel: the variance contraction, timed live with HIP events on its stream) and
+A plain run sets up, warms up, times the K steps and has rank 0 print ONE JSON line (the
+driver contract) with the headline `value` and `ms_per_step`.  --dump-outputs DIR also writes
+the last timed job's posterior mean and variance as DIR/<name>.npy (same arguments, same
+inputs, so two builds can be compared output for output).  --full adds every other reading
+to the line, each from a run of its own: `roofline` (dominant kernel: the variance
+contraction, timed live with HIP events on its stream), `unpipelined`, `single_job`,
+`mean_only_value`, the strict FP64 engine and the Krig drop-in surface (N = 1), and
 `cpu_baseline` (the numpy oracle on the host cores, bounded sample, N = 1 only).
 """
 from __future__ import annotations
@@ -53,6 +58,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed jobs (default 100; --config D: 4, E: 2 sweeps)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also take every secondary reading (roofline, unpipelined, "
+                         "single_job, mean-only, FP64 engine, drop-in surface, CPU baseline), each a run of its own")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (posterior mean and "
+                         "variance; config E: LML and gradient per setting) as DIR/<name>.npy")
     ap.add_argument("--ntrain", type=int, default=4096)
     ap.add_argument("--grid", type=int, default=256)
     ap.add_argument("--kind", default="df")
@@ -88,10 +99,10 @@ def parse():
                          "does (the steps are independent fit+predict jobs, like the reference's per-time-window "
                          "krig.kriging loop); 0 = strictly one job after the other")
     ap.add_argument("--unpipelined-steps", type=int, default=20,
-                    help="with --pipeline 1 on one rank: first time this many jobs strictly one after another "
+                    help="--full, with --pipeline 1 on one rank: first time this many jobs strictly one after another "
                          "(reported under 'unpipelined', with the dominant kernel's roofline alone)")
     ap.add_argument("--cpu-baseline", type=int, default=-1,
-                    help="time the numpy oracle on the host cores (N=1 only); -1 = only when N_train <= 4096")
+                    help="--full: time the numpy oracle on the host cores (N=1 only); -1 = only when N_train <= 4096")
     ap.add_argument("--cpu-sample-points", type=int, default=2048)
     ap.add_argument("--pmc-json", default=None)
     ap.add_argument("--fits-ahead", type=int, default=None,
@@ -110,11 +121,11 @@ def parse():
                     help="config E: settings per batched factorisation (hyper.sweep batch; default: the "
                          "library's hyper.auto_batch)")
     ap.add_argument("--single-job-dist", type=int, default=0,
-                    help="also time one job with distributed.fit_distributed at N = 1 (always at N > 1)")
+                    help="--full: also time one job with distributed.fit_distributed at N = 1 (always at N > 1)")
     ap.add_argument("--f64-steps", type=int, default=5,
-                    help="N = 1: also time this many jobs of the same stream on the strict FP64 engine (f64_value)")
+                    help="--full, N = 1: also time this many jobs of the same stream on the strict FP64 engine (f64_value)")
     ap.add_argument("--dropin-steps", type=int, default=3,
-                    help="N = 1: also time this many krig.Krig(...).fit(...).predict_device(grid) jobs (dropin)")
+                    help="--full, N = 1: also time this many krig.Krig(...).fit(...).predict_device(grid) jobs (dropin)")
     a = ap.parse_args()
     if a.config == "B":
         a.kind, a.ntrain, a.grid = "df", 1024, 128
@@ -238,6 +249,25 @@ def cpu_baseline(x, y, xg, kind, l, noise, sample_pts):
                       f"grid points ({t2 - t1:.2f} s), predict extrapolated linearly; OpenBLAS threads={cores}"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict, ws: int, rank: int):
+    """--dump-outputs: each array (device tensor or numpy) as <path>/<name>.npy in float64
+    (N > 1: <name>_rank<r>.npy, this rank's shard).  Above DUMP_LIMIT_BYTES in all, every array
+    is cut to an equal share: a fixed, seeded sample of its flattened elements, in index order."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: np.ascontiguousarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64)
+            for k, v in arrays.items() if v is not None}
+    if sum(a.nbytes for a in host.values()) > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (8 * len(host))
+        rng = np.random.default_rng(2016)
+        host = {k: a if a.size <= keep else a.ravel()[np.sort(rng.choice(a.size, keep, replace=False))]
+                for k, a in host.items()}
+    for k, a in host.items():
+        np.save(os.path.join(path, k + (f"_rank{rank}" if ws > 1 else "") + ".npy"), a)
+
+
 def _pmc_round(path: str, pmc: dict) -> str:
     """The round a PMC pass belongs to: its 'round' field, else the rNN prefix of the file or of
     its directory (profiles/r04_pmc_traffic_ozaki.json, gpurun_out/r04/pmc_traffic_ozaki.json)."""
@@ -295,6 +325,8 @@ def run_sweep(args, ws, rank, dev):
     if is_multi(ws):
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     elapsed = float(dt.item())
+    if args.dump_outputs and rank == 0:   # all-reduced: every rank holds the same values
+        dump_outputs(args.dump_outputs, {"lml": vals, "lml_grad": grads}, 1, 0)
     if rank == 0:
         n = 2 * E.padded_points(args.ntrain)
         # per setting: POTRF n³/3 + TRTRI n³/3 + K_y⁻¹ = WᵀW n³/3 (FP64 MFMA), the rest O(n²)
@@ -547,7 +579,7 @@ def main():
     else:
         set_mode(cfg["mode"])
     unpiped = None
-    if cfg["pipeline"] and not is_multi(ws) and args.unpipelined_steps > 0:
+    if args.full and cfg["pipeline"] and not is_multi(ws) and args.unpipelined_steps > 0:
         # reference: the same jobs strictly one after another, measured BEFORE the timed region
         # (the dominant kernel's launch time without a concurrent fit = its roofline alone)
         cfg["pipeline"] = False
@@ -591,19 +623,24 @@ def main():
     trace = os.environ.get("GP2D_BENCH_TRACE") == "1"   # per-step wall times on stderr (diagnostics)
 
     def run_jobs(k, t_ref=None):
+        """Run k jobs; returns what the last one handed its caller: (mean, var) device tensors."""
         it = stream(k) if stream is not None else (step() for _ in range(k))
-        for i, _ in enumerate(it):
+        last = None
+        for i, last in enumerate(it):
             if trace and t_ref is not None:
                 torch.cuda.synchronize()
                 print(f"[rank {rank}] step {i}: {1e3 * (time.perf_counter() - t_ref):.1f} ms since start",
                       file=sys.stderr, flush=True)
+        # a job stream yields (mean, var) or (lo, hi, mean, var); step() fills the (mean, var) buffers
+        return tuple(last[-2:]) if stream is not None and last is not None else (mean, var)
 
     # round robin: at least one warmup job per rank, so every rank has fitted before the clock
     warm = max(args.warmup, ws) if cfg["mode"] == "rr" else args.warmup
     run_jobs(warm)
     barrier(ws)
-    E.timing_enable(True)
-    E.timing_read()
+    if args.full:   # the dominant kernel's launches of the timed jobs, for `roofline`
+        E.timing_enable(True)
+        E.timing_read()
     stats.clear()
     if comm is not None:
         comm.clear()
@@ -612,13 +649,16 @@ def main():
     t0 = time.perf_counter()
     if marks:
         E.N.lib().gp2d_trace_mark(1, E._stream_handle(dev))
-    run_jobs(args.steps, t0)
+    last = run_jobs(args.steps, t0)
     if marks:
         E.N.lib().gp2d_trace_mark(2, E._stream_handle(dev))
     barrier(ws)
     t1 = time.perf_counter()
-    kms, klaunch, kflops = E.timing_read()
-    E.timing_enable(False)
+    if args.full:
+        kms, klaunch, kflops = E.timing_read()
+        E.timing_enable(False)
+    if args.dump_outputs:   # before any later reading reuses the result buffers
+        dump_outputs(args.dump_outputs, {"mean": last[0], "var": last[1]}, ws, rank)
     # fits issued inside [t0, t1] on this rank (all of this rank's fits of the timed jobs)
     fit_times = stats.get("fit_issue_times", [])
     fits = torch.tensor([sum(t0 <= t <= t1 for t in fit_times), len(fit_times)], dtype=torch.float64, device=dev)
@@ -647,7 +687,47 @@ def main():
         comm_out["transport"] = ("the library's own RCCL communicator (gp2d_comm_init; gp2d_bcast on the comm stream)"
                                  if lc is not None else f"torch.distributed ({dist.get_backend()}) rehearsal")
         comm_out["library_calls"] = dict(lc.calls) if lc is not None else None
+    out = {
+        "metric": METRIC if (args.kind, args.ntrain) == ("df", 4096) else
+        f"posterior grid points/sec (fit+predict), N_train={args.ntrain}, {args.kind} 2D kernel",
+        "value": value,
+        "unit": "points/s",
+        "n_gpus": ws,
+        "world_size": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f64" if args.variance == "f64" else "f64 (variance GEMM as exact int8 Ozaki-II)",
+        "data": "synthetic (seeded drifter field, SURVEY.md §8d)",
+        "config": {"workload": f"{args.kind} kernel, N_train={args.ntrain}, " +
+                               (f"one {G}x{G} grid sharded over {ws} GPU(s)" if strong else f"{G}x{G} grid per GPU") +
+                               ", fit+predict (mean+variance)" + (f" [BASELINE config {args.config}]" if args.config else ""),
+                   "n_train": args.ntrain, ("grid_global" if strong else "grid_per_gpu"): f"{G}x{G}",
+                   "points_total": m_all, "length_scale_km": 5.0, "noise": noise,
+                   "parallelism": (f"grid-sharded x{ws}, job j fitted on rank j mod {ws}, factor broadcast "
+                                   "(RCCL, packed W)" if cfg["mode"] == "rr" else
+                                   f"grid-sharded x{ws}, factor {cfg['mode']}" +
+                                   (" (RCCL broadcast of packed W)" if is_multi(ws) and cfg["mode"] == "bcast" else "")),
+                   "fit_mode_probe_ms_per_step": probe or None, "kstar_ahead": cfg["ahead"]},
+        "pipelined": cfg["pipeline"],
+        "api": api,
+        **job_stream_shape(args, spec, m, api),
+        "timed_fits": timed_fits,
+        "guard": guard,
+    }
+    if comm_out is not None:
+        out["comm"] = comm_out
+    if not args.full:   # a plain run ends here: the headline line alone
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if is_multi(ws):
+            finish_dist()
+        return
 
+    # --full: every other reading, each from a run of its own
     # one job alone (unpipelined, its grid sharded over the ranks; at N > 1 fitted on rank 0 and
     # broadcast): the single-job reading beside the job-stream value
     reps = 1 if args.ntrain > 8192 else 3
@@ -740,43 +820,7 @@ def main():
                 "kernel": "gemm_f64_kernel<NN,COLSQ> (variance ‖L⁻¹k*‖²)",
                 "launches": klaunch, "avg_launch_ms": (kms / klaunch) if klaunch else None,
                 "flops_per_launch": (kflops / klaunch) if klaunch else None}
-    out = {
-        "metric": METRIC if (args.kind, args.ntrain) == ("df", 4096) else
-        f"posterior grid points/sec (fit+predict), N_train={args.ntrain}, {args.kind} 2D kernel",
-        "value": value,
-        "unit": "points/s",
-        "n_gpus": ws,
-        "world_size": ws,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong" if strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f64" if args.variance == "f64" else "f64 (variance GEMM as exact int8 Ozaki-II)",
-        "data": "synthetic (seeded drifter field, SURVEY.md §8d)",
-        "config": {"workload": f"{args.kind} kernel, N_train={args.ntrain}, " +
-                               (f"one {G}x{G} grid sharded over {ws} GPU(s)" if strong else f"{G}x{G} grid per GPU") +
-                               ", fit+predict (mean+variance)" + (f" [BASELINE config {args.config}]" if args.config else ""),
-                   "n_train": args.ntrain, ("grid_global" if strong else "grid_per_gpu"): f"{G}x{G}",
-                   "points_total": m_all, "length_scale_km": 5.0, "noise": noise,
-                   "parallelism": (f"grid-sharded x{ws}, job j fitted on rank j mod {ws}, factor broadcast "
-                                   "(RCCL, packed W)" if cfg["mode"] == "rr" else
-                                   f"grid-sharded x{ws}, factor {cfg['mode']}" +
-                                   (" (RCCL broadcast of packed W)" if is_multi(ws) and cfg["mode"] == "bcast" else "")),
-                   "fit_mode_probe_ms_per_step": probe or None, "kstar_ahead": cfg["ahead"]},
-        "roofline": roof,
-        "pipelined": cfg["pipeline"],
-        "api": api,
-        **job_stream_shape(args, spec, m, api),
-        "unpipelined": unpiped,
-        "single_job": single_job,
-        "timed_fits": timed_fits,
-        "mean_only_value": mean_only,
-        "guard": guard,
-    }
-    if comm_out is not None:
-        out["comm"] = comm_out
+    out.update(roofline=roof, unpipelined=unpiped, single_job=single_job, mean_only_value=mean_only)
     if not is_multi(ws):
         out.update(extra_readings_n1(args, spec, xt, yt, noise, xg, m_all))
     if not is_multi(ws) and (args.cpu_baseline > 0 or (args.cpu_baseline < 0 and args.ntrain <= 4096)):

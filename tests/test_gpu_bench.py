@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.parametrize("variance", ["ozaki", "f64"])
 def test_bench_json_contract(variance):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--ntrain", "256", "--grid", "32", "--steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--ntrain", "256", "--grid", "32", "--steps", "2",
            "--warmup", "1", "--chunk", "1024", "--cpu-sample-points", "64", "--variance", variance]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=100, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -48,6 +48,37 @@ def test_bench_json_contract(variance):
     assert d["batch_ahead"] is False or (d["fits_ahead"] == 0 and d["batch_fits"] > 1)
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline only (no secondary reading is taken), and
+    --dump-outputs writes the last timed job's mean and variance: float64, and bit for bit what
+    engine.fit + engine.predict return for the bench's seeded inputs (krige_jobs' contract)."""
+    import numpy as np
+    from gp2d import data as D
+    from gp2d import engine as E
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--ntrain", "256", "--grid", "32",
+           "--steps", "3", "--warmup", "1", "--chunk", "1024", "--dump-outputs", str(tmp_path / "dump")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=100, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["timed_fits"]["issued_in_window"] == d["timed_fits"]["issued_total"] == 3
+    assert abs(d["value"] - 32 * 32 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for key in ("roofline", "cpu_baseline", "unpipelined", "single_job", "mean_only_value", "f64", "dropin"):
+        assert key not in d, key
+    assert sorted(os.listdir(tmp_path / "dump")) == ["mean.npy", "var.npy"]
+    mean, var = (np.load(tmp_path / "dump" / f) for f in ("mean.npy", "var.npy"))
+    assert mean.dtype == var.dtype == np.float64 and mean.shape == var.shape == (2 * 32 * 32,)
+    x1, x2, u, v = D.synthetic_tracks(256, seed=2016)
+    _, _, xg = D.bbox_grid(x1, x2, 32, pad=5.0)
+    gp = E.fit(E.KernelSpec(kind="df", l_df=5.0, l_cf=5.0, ratio=1.0), np.stack([x1, x2], 1), np.concatenate([u, v]),
+               0.0025, device="cuda:0", variance="ozaki")
+    mu, va = E.predict(gp, xg, chunk=1024)
+    assert np.array_equal(mean, mu.cpu().numpy()) and np.array_equal(var, va.cpu().numpy())
+
+
 def test_bench_two_ranks_default_contract():
     """The N > 1 default (strong scaling, round-robin fits + factor broadcast) through
     torch.distributed.run with two ranks on the one card (gloo: RCCL refuses two ranks per
@@ -60,7 +91,7 @@ def test_bench_two_ranks_default_contract():
     env = dict(os.environ, GP2D_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--ntrain", "256", "--grid", "64", "--steps", "4", "--warmup", "1", "--chunk", "1024"]
+           "--full", "--ntrain", "256", "--grid", "64", "--steps", "4", "--warmup", "1", "--chunk", "1024"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=200, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -101,7 +132,7 @@ def test_bench_multi_rank_paths_under_rccl():
     env.pop("GP2D_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1",
-           "--ntrain", "700", "--grid", "64", "--steps", "3", "--warmup", "1", "--chunk", "1024"]
+           "--full", "--ntrain", "700", "--grid", "64", "--steps", "3", "--warmup", "1", "--chunk", "1024"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=200, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -1,7 +1,9 @@
+# Round-end record, from the repository root on a GPU host: the GPU tests, smoke() and the full
+# benchmark line, kept under $OUT/<name> (default build/<name>).  usage: bash tools/gpu_round_end.sh [name]
 set -o pipefail
 R=${1:-round_end}
-mkdir -p gpurun_out/$R
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > gpurun_out/$R/gpu_tests.log 2>&1 && \
-timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/$R/smoke.txt 2>&1 && \
-timeout -k 10 400 python -u bench.py > gpurun_out/$R/bench.json 2> gpurun_out/$R/bench.err
+OUT=${OUT:-build}/$R
+mkdir -p "$OUT"
+timeout -k 10 900 python -u -m pytest tests -m gpu -x -q > "$OUT/gpu_tests.log" 2>&1 && \
+timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.txt" 2>&1 && \
+timeout -k 10 400 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"

@@ -7,8 +7,8 @@ critical-path chain (`potrf_diag_kernel`, `gemm_f64_panel_kernel`) and the rest 
 
     python tools/overlap_attrib.py <results.db> [first igemm launch of the window] [launches]
 
-Default window: bench.py's timed region of 20 jobs (20 × 96 launches), which the three
-single-job launches (3 × 96) follow.
+Default window: the timed region of 20 jobs (20 × 96 launches) of `bench.py --full`, which the
+three single-job launches (3 × 96) follow.
 """
 import collections
 import sqlite3

@@ -13,7 +13,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$R
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="bench.py --steps 1 --warmup 1 --cpu-baseline 0 --pipeline 0 --variance $V"
+B="bench.py --full --steps 1 --warmup 1 --cpu-baseline 0 --pipeline 0 --variance $V"
 csv() { find "$1" -name "*counter_collection.csv" | head -n 1; }
 if [ "$V" = ozaki ]; then
   timeout -s KILL 120 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES -f csv -d "$OUT/pmc_clock_$V" -o run -- \
@@ -29,7 +29,7 @@ else
     "gemm_f64_kernel<false, 1>" > /dev/null
 fi
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof_$V" -o run -- \
-  python3 bench.py --steps 5 --warmup 2 --cpu-baseline 0 --variance "$V" --pmc-json "$OUT/pmc_traffic_$V.json" \
+  python3 bench.py --full --steps 5 --warmup 2 --cpu-baseline 0 --variance "$V" --pmc-json "$OUT/pmc_traffic_$V.json" \
   > "$OUT/prof_$V.log" 2>&1
-timeout -k 10 400 python3 bench.py --variance "$V" --pmc-json "$OUT/pmc_traffic_$V.json" > "$OUT/bench_$V.json" 2> "$OUT/bench_$V.err"
+timeout -k 10 400 python3 bench.py --full --variance "$V" --pmc-json "$OUT/pmc_traffic_$V.json" > "$OUT/bench_$V.json" 2> "$OUT/bench_$V.err"
 cat "$OUT/bench_$V.json"

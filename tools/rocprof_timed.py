@@ -1,6 +1,6 @@
 """The dominant kernel's average duration over bench.py's TIMED region, from a rocprofv3
 --kernel-trace of the exact bench command (the roofline must reproduce
-from profiles/).  bench.py's one-rank run launches, in order: `warmup` + `unpipelined_steps`
+from profiles/).  bench.py's one-rank --full run launches, in order: `warmup` + `unpipelined_steps`
 unpipelined jobs, `warmup` pipelined warmup jobs, the `steps` timed jobs, then the single-job
 reps; every job launches the same number of int8 GEMMs (nmod × chunks), so the timed region
 is a fixed index range of the kernel's dispatches.
