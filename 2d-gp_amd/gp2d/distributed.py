@@ -130,8 +130,7 @@ def broadcast_fit(gp: E.GPFit | None, spec: E.KernelSpec, noise: float, x, devic
                           device=dev, n_mat=n)
             E.ozaki_prepare(out, diag_add=float(planes_only), packed=packed)
         # the owner's guard statistics arrive in the status block: check() applies the same rule
-        out.extra["guard"] = dict(pending=True, diag_add=float(planes_only),
-                                  stream=torch.cuda.current_stream(dev))
+        E._arm_guard(out, planes_only)
     else:
         with _timed(comm, "recv_prepare", False, 0, ws, recv=0, device=dev):
             W = torch.zeros((n, n), dtype=torch.float64, device=dev)   # the strict upper part stays 0
@@ -139,8 +138,7 @@ def broadcast_fit(gp: E.GPFit | None, spec: E.KernelSpec, noise: float, x, devic
             out = E.GPFit(kernel=spec, noise=float(noise), x=X, n_train=ntr, n_pad=npad, W=W, alpha=alpha, device=dev)
             if planes_only is not None and RECV_UNPACK:   # the round-4 receive path (measurement only)
                 E.ozaki_prepare(out, diag_add=float(planes_only))
-                out.extra["guard"] = dict(pending=True, diag_add=float(planes_only),
-                                          stream=torch.cuda.current_stream(dev))
+                E._arm_guard(out, planes_only)
         if wbits is not None and wbits != 0:   # the owner's guard decision, applied as is
             out.extra["guard"] = dict(pending=False, engine="f64" if wbits < 0 else "ozaki",
                                       wbits=None if wbits < 0 else wbits, kbits=None if wbits < 0 else kbits)
@@ -323,21 +321,11 @@ def fit_distributed(spec: E.KernelSpec, x, y, noise: float, device=None, varianc
     dev = E._require_device(device)
     if variance not in E.VARIANCE_ENGINES:
         raise ValueError(f"variance must be one of {E.VARIANCE_ENGINES}")
-    if variance == "ozaki" and not spec.is_vector:
-        raise ValueError("the ozaki variance engine supports the vector families only")
     L = E.N.lib()
-    d, bd = spec.input_dim, spec.block_dim
-    X = E._as_points(x, d, dev)
-    ntr = X.shape[0]
-    if ntr < 1:
-        raise ValueError("need at least one training point")
-    npad, n = dfact_layout(spec, ntr)   # n a multiple of the super-block
+    # n a multiple of the super-block
+    staged = E._stage_problem(spec, x, variance, dev, layout=lambda k, ntr, _: dfact_layout(k, ntr))
+    X, ntr, npad, n = staged.X, staged.ntr, staged.npad, staged.n
     SB = super_block()
-    if variance == "ozaki" and n >= 131072:
-        raise ValueError(f"the ozaki variance engine supports n < 131072; got n = {n}")
-    perm = None
-    if variance == "ozaki" and ntr > 1:
-        perm, X = E.morton_sort(X)
     main = torch.cuda.current_stream(dev)
     sh = E._stream_handle(dev)
     P = E._ptr
@@ -359,7 +347,7 @@ def fit_distributed(spec: E.KernelSpec, x, y, noise: float, device=None, varianc
     pdoubles = int(L.gp2d_dfact_panel_doubles(n))
     panels = [torch.empty(pdoubles, dtype=torch.float64, device=dev) for _ in range(2)]
     wbytes = int(L.gp2d_dfact_workspace(n))
-    work = torch.empty(wbytes // 8 + 1, dtype=torch.float64, device=dev)
+    work = E._workspace(wbytes, dev)
     info = torch.zeros(1, dtype=torch.int32, device=dev)   # the owners' panels only ever raise it
     cstream = E.side_stream(dev)
     t0 = time.perf_counter()
@@ -445,10 +433,9 @@ def fit_distributed(spec: E.KernelSpec, x, y, noise: float, device=None, varianc
             if t % ws != rank and t > 0:
                 A[:t * SB, t * SB:(t + 1) * SB].zero_()
     t2 = time.perf_counter()
-    Y = E._pad_obs(y, ntr, npad, bd, dev, perm)
+    Y = E._pad_obs(y, ntr, npad, spec.block_dim, dev, staged.perm)
     alpha = _alpha_owned(A, n, Y, ws, rank, nsb, SB, dev, collective=not _solo(ws) and emulate is None, comm=comm)
-    gp = E.GPFit(kernel=spec, noise=float(noise), x=X, n_train=ntr, n_pad=npad, W=A, alpha=alpha, device=dev,
-                 y=Y, perm=perm)
+    gp = E._make_fit(staged, noise, A, alpha, Y, dev)
     if emulate is not None:
         return gp
     E._raise_fit_errors(int(info.item()), None)
@@ -490,7 +477,7 @@ def _alpha_owned(A: torch.Tensor, n: int, Y: torch.Tensor, ws: int, rank: int, n
     ab = torch.zeros((cap, SB), dtype=torch.float64, device=dev)
     if mine:
         wb = int(L.gp2d_dfact_alpha_workspace(n, len(mine)))
-        work = torch.empty(wb // 8 + 1, dtype=torch.float64, device=dev)
+        work = E._workspace(wb, dev)
         E.N.check(L.gp2d_dfact_alpha_blocks(P(A), n, n, mine[0], dt, len(mine), P(z), P(ab), P(work), wb, sh),
                   "gp2d_dfact_alpha_blocks")
     if not collective:
@@ -673,9 +660,7 @@ def krige_jobs_sharded(jobs, variance: str = "ozaki", chunk: int = 8192, var_mod
         main.wait_event(ready)
         gp.ready_on(main)
         gp.record_stream(main)
-        if pred is None or not pred.fits(gp):
-            pred = E.Predictor(gp, chunk)
-        pred.gp = gp
+        pred = E._predictor_for(pred, gp, chunk)
         out = predict_shard(pred, E._as_points(xg, spec.input_dim, dev), var_mode=var_mode,
                             compute_var=compute_var, align=align)
         refill()

@@ -12,6 +12,7 @@ Reference call sites replaced:
 from __future__ import annotations
 
 import collections
+import contextlib
 import os
 import ctypes
 import itertools
@@ -33,6 +34,11 @@ def _stream_handle(device) -> ctypes.c_void_p:
 
 def _ptr(t: torch.Tensor) -> ctypes.c_void_p:
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    """Device scratch of at least `nbytes` bytes (the library's *_workspace counts), 8-byte aligned."""
+    return torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=device)
 
 
 def _require_device(device=None) -> torch.device:
@@ -105,31 +111,6 @@ def side_stream(device=None) -> torch.cuda.Stream:
     pool streams 6 and 10 of 12 did, profiles/r03_queue_aliasing.json); the high-priority pool is
     a different set of queues."""
     return torch.cuda.Stream(device, priority=-1)
-
-
-class MaskedStream:
-    """A HIP stream restricted to the CUs of mask bits [first, first + count)
-    (gp2d_stream_create_cumask; bit i lies in XCD i mod 8), usable as a torch stream
-    (`.stream`, a torch.cuda.ExternalStream); destroyed with the object."""
-
-    def __init__(self, first: int, count: int, device=None):
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        h = ctypes.c_void_p()
-        with torch.cuda.device(dev):
-            N.check(N.lib().gp2d_stream_create_cumask(int(first), int(count), ctypes.byref(h)),
-                    "gp2d_stream_create_cumask")
-        self.handle = h
-        self.stream = torch.cuda.ExternalStream(h.value, device=dev)
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h is not None and h.value:
-            try:
-                torch.cuda.synchronize(self.stream.device)
-                N.lib().gp2d_stream_destroy(h)
-            except Exception:   # noqa: BLE001 — interpreter shutdown
-                pass
-            self.handle = None
 
 
 def _as_points(x, dim: int, device) -> torch.Tensor:
@@ -249,11 +230,10 @@ class GPFit:
             host, ev, err = self.pending
             self.pending = None
             ev.synchronize()
-            inf = int(host.view(torch.int32)[0].item())
-            vmin, wmax = float(host[1].item()), float(host[2].item())
-            _PINNED_STATUS.append(host)
-            _raise_fit_errors(inf, err)
-            apply_guard(self, vmin, wmax)
+            try:
+                _settle(self, host, err)
+            finally:
+                _PINNED_STATUS.append(host)
         return self
 
     def record_stream(self, stream) -> "GPFit":
@@ -437,11 +417,145 @@ def ozaki_prepare_guarded(gp: GPFit, diag_add: float, guard: bool = True) -> GPF
     status, _ = status_block(gp.device)
     _guard_stats(gp.W, gp.n, gp.n_train, gp.n_pad, diag_add, status, gp.device)
     host = status.cpu()
-    gp.extra["guard"] = dict(pending=True, diag_add=float(diag_add), stream=torch.cuda.current_stream(gp.device))
+    _arm_guard(gp, diag_add)
     apply_guard(gp, float(host[1]), float(host[2]))
     if "ozaki" not in gp.extra and gp.extra["guard"]["engine"] == "ozaki":
         ozaki_prepare(gp, diag_add=float(diag_add))
     return gp.ready_on(torch.cuda.current_stream(gp.device))
+
+
+# ------------------------------------------------------------------ the fit's stages
+# (shared by fit, fit_batch, distributed.fit_distributed and krig.Krig._restore)
+@dataclass
+class _Staged:
+    """One problem ready for assembly (_stage_problem): the training points in fit order (Morton
+    for the ozaki engine, x = x_input[perm]) and the fit's layout."""
+    kernel: KernelSpec
+    X: torch.Tensor
+    ntr: int
+    npad: int
+    n: int
+    perm: torch.Tensor | None
+
+
+def _check_family(kernel: KernelSpec, variance: str):
+    if variance == "ozaki" and not kernel.is_vector:
+        raise ValueError("the ozaki variance engine supports the vector families only")
+
+
+def _stage_problem(kernel: KernelSpec, x, variance: str, dev, layout=fit_layout) -> _Staged:
+    """Points on the device, the layout ((padded points, matrix order) = layout(kernel, N_train,
+    variance)), the ozaki engine's size limit and its Morton order."""
+    _check_family(kernel, variance)
+    X = _as_points(x, kernel.input_dim, dev)
+    ntr = X.shape[0]
+    if ntr < 1:
+        raise ValueError("need at least one training point")
+    npad, n = layout(kernel, ntr, variance)
+    if variance == "ozaki" and n >= 131072:
+        # the int8 GEMM epilogue's biased sums stay below 2^32 only for K = n < 2^17
+        raise ValueError(f"the ozaki variance engine supports n < 131072 (N_train < 65536); got n = {n}: "
+                         "use variance='f64'")
+    perm = None
+    if variance == "ozaki" and ntr > 1:   # Morton order: exact-zero K* slabs cluster (skipped)
+        perm, X = morton_sort(X)
+    return _Staged(kernel, X, ntr, npad, n, perm)
+
+
+def _assemble_ky(st: _Staged, diag_add: float, A: torch.Tensor, dev):
+    """K_y = K(x, x) + diag_add·I into A (n × n) — for the vector families its lower block
+    triangle only (symmetric = 2), all gp2d_potrf reads."""
+    N.check(N.lib().gp2d_assemble(_ptr(st.X), st.ntr, st.npad, _ptr(st.X), st.ntr, st.npad,
+                                  ctypes.byref(st.kernel.desc()), float(diag_add),
+                                  ASSEMBLE_LOWER if st.kernel.is_vector else 1, _ptr(A), st.n, _stream_handle(dev)),
+            "gp2d_assemble")
+
+
+@contextlib.contextmanager
+def _factor_join(on: bool):
+    """gp2d_factor_join(on) for the factorisations issued inside; the previous mode comes back."""
+    prev = N.lib().gp2d_factor_join(1 if on else 0)
+    try:
+        yield
+    finally:
+        N.lib().gp2d_factor_join(prev)
+
+
+def _factor_inverse(A: torch.Tensor, n: int, dinv: torch.Tensor, info: torch.Tensor, dev, join: bool | None = None):
+    """A ← W = L⁻¹, L = chol(A): gp2d_potrf then gp2d_trtri, or gp2d_potrf_inv when FUSED_INVERSE.
+    join: the gp2d_factor_join mode around the factorisation (None: left as it is)."""
+    L = N.lib()
+    s = _stream_handle(dev)
+    with (contextlib.nullcontext() if join is None else _factor_join(join)):
+        if FUSED_INVERSE:   # factor and inverse in one call, the TRTRI GEMMs overlapped with POTRF
+            wbytes = int(L.gp2d_potrf_inv_workspace(n))
+            work = _workspace(wbytes, dev)
+            N.check(L.gp2d_potrf_inv(_ptr(A), n, n, _ptr(dinv), _ptr(info), _ptr(work), wbytes, s),
+                    "gp2d_potrf_inv")
+            return
+        N.check(L.gp2d_potrf(_ptr(A), n, n, _ptr(dinv), _ptr(info), None, 0, s), "gp2d_potrf")
+    wbytes = int(L.gp2d_trtri_workspace(n))
+    work = _workspace(wbytes, dev)
+    N.check(L.gp2d_trtri(_ptr(A), n, n, _ptr(dinv), _ptr(work), wbytes, s), "gp2d_trtri")
+
+
+def _arm_guard(gp: GPFit, diag_add: float):
+    """Arm the accuracy guard of a fit whose statistics are still to come: apply_guard acts on
+    exactly these keys, once, on the stream that is current now."""
+    gp.extra["guard"] = dict(pending=True, diag_add=float(diag_add), stream=torch.cuda.current_stream(gp.device))
+
+
+def _make_fit(st: _Staged, noise: float, W: torch.Tensor, alpha: torch.Tensor, Y: torch.Tensor, dev) -> GPFit:
+    return GPFit(kernel=st.kernel, noise=float(noise), x=st.X, n_train=st.ntr, n_pad=st.npad, W=W, alpha=alpha,
+                 device=dev, y=Y, perm=st.perm)
+
+
+def _finish_problem(st: _Staged, W: torch.Tensor, y, noise: float, diag_add: float, status: torch.Tensor,
+                    guard: bool | None, variance: str, check: bool, dev, pwork: torch.Tensor | None = None):
+    """Everything of a fit after W = L⁻¹, queued on the current stream: the guard's statistics
+    beside info in `status` (status_block), the status copy of a check=False fit (it reads only
+    words written before it, so the host later waits for the factor, not for what follows), α, and
+    the ozaki engine's planes at the default precision.  pwork: a gp2d_potrs workspace shared by a
+    batch's problems.  Returns (fit, the preparation's deferred GP2DError or None); check=False
+    leaves both with the copy in fit.pending for GPFit.check()."""
+    L = N.lib()
+    n = st.n
+    guard = (GUARD_DEFAULT if guard is None else guard) and variance == "ozaki"
+    if guard:   # the guard's statistics from W, into the status word beside info
+        _guard_stats(W, n, st.ntr, st.npad, diag_add, status, dev)
+    else:       # "no guard ran": a receiving rank of the job stream keeps the default precision
+        status[1:].fill_(float("nan"))
+    pend = None if check else pending_status(status)
+    Y = _pad_obs(y, st.ntr, st.npad, st.kernel.block_dim, dev, st.perm)
+    alpha = torch.empty(n, dtype=torch.float64, device=dev)
+    pbytes = int(L.gp2d_potrs_workspace(n))
+    if pwork is None:
+        pwork = _workspace(pbytes, dev)
+    N.check(L.gp2d_potrs_inv(_ptr(W), n, n, _ptr(Y), _ptr(alpha), _ptr(pwork), pbytes, _stream_handle(dev)),
+            "gp2d_potrs_inv")
+    gp = _make_fit(st, noise, W, alpha, Y, dev)
+    gp.extra["status_dev"] = status   # info + guard statistics on the device (the job stream broadcasts it)
+    del pwork
+    err = None
+    if variance == "ozaki":
+        # enqueued before the status is read, with the a-priori moduli count at the default
+        # precision: the fit's only host round trip is the status read
+        if guard:
+            _arm_guard(gp, diag_add)
+        try:
+            ozaki_prepare(gp, diag_add=float(diag_add))
+        except N.GP2DError as e:   # a failed factor (NaN rows) makes prepare fail too: info decides
+            err = e
+    if pend is not None:
+        gp.pending = (pend[0], pend[1], err)
+    return gp, err
+
+
+def _settle(gp: GPFit, host: torch.Tensor, err) -> GPFit:
+    """A fit's ending once its status block is on the host: raise what the factor or the
+    preparation left, then the accuracy guard."""
+    _raise_fit_errors(int(host.view(torch.int32)[0].item()), err)
+    return apply_guard(gp, float(host[1]), float(host[2]))
 
 
 def fit(kernel: KernelSpec, x, y, noise: float, jitter: float = 0.0, device=None, variance: str = "f64",
@@ -492,84 +606,18 @@ def fit(kernel: KernelSpec, x, y, noise: float, jitter: float = 0.0, device=None
             raise np.linalg.LinAlgError("not positive definite, even with jitter.") from None
     if variance not in VARIANCE_ENGINES:
         raise ValueError(f"variance must be one of {VARIANCE_ENGINES}")
-    if variance == "ozaki" and not kernel.is_vector:
-        raise ValueError("the ozaki variance engine supports the vector families only")
+    _check_family(kernel, variance)   # before the device is required, like the check above
     dev = _require_device(device)
-    L = N.lib()
-    d, bd = kernel.input_dim, kernel.block_dim
-    X = _as_points(x, d, dev)
-    ntr = X.shape[0]
-    if ntr < 1:
-        raise ValueError("need at least one training point")
-    npad, n = fit_layout(kernel, ntr, variance)
-    if variance == "ozaki" and n >= 131072:
-        # the int8 GEMM epilogue's biased sums stay below 2^32 only for K = n < 2^17
-        raise ValueError(f"the ozaki variance engine supports n < 131072 (N_train < 65536); got n = {n}: "
-                         "use variance='f64'")
-    perm = None
-    if variance == "ozaki" and ntr > 1:   # Morton order: exact-zero K* slabs cluster (skipped)
-        perm, X = morton_sort(X)
-    s = _stream_handle(dev)
-    desc = kernel.desc()
+    st = _stage_problem(kernel, x, variance, dev)
+    n, diag_add = st.n, noise + jitter
     A = torch.empty((n, n), dtype=torch.float64, device=dev)
-    # the vector families: K_y's lower block triangle only (symmetric = 2), all gp2d_potrf reads
-    N.check(L.gp2d_assemble(_ptr(X), ntr, npad, _ptr(X), ntr, npad, ctypes.byref(desc), float(noise + jitter),
-                            ASSEMBLE_LOWER if kernel.is_vector else 1, _ptr(A), n, s), "gp2d_assemble")
+    _assemble_ky(st, diag_add, A, dev)
     dinv = torch.empty((n // NB, NB, NB), dtype=torch.float64, device=dev)
     status, info = status_block(dev)   # gp2d_potrf resets info
-    prev_join = L.gp2d_factor_join(1 if (check if join is None else join) else 0)
-    try:
-        if FUSED_INVERSE:   # factor and inverse in one call, the TRTRI GEMMs overlapped with POTRF
-            wbytes = int(L.gp2d_potrf_inv_workspace(n))
-            work = torch.empty(wbytes // 8 + 1, dtype=torch.float64, device=dev)
-            N.check(L.gp2d_potrf_inv(_ptr(A), n, n, _ptr(dinv), _ptr(info), _ptr(work), wbytes, s),
-                    "gp2d_potrf_inv")
-        else:
-            N.check(L.gp2d_potrf(_ptr(A), n, n, _ptr(dinv), _ptr(info), None, 0, s), "gp2d_potrf")
-    finally:
-        L.gp2d_factor_join(prev_join)
-    if not FUSED_INVERSE:
-        wbytes = int(L.gp2d_trtri_workspace(n))
-        work = torch.empty(wbytes // 8 + 1, dtype=torch.float64, device=dev)
-        N.check(L.gp2d_trtri(_ptr(A), n, n, _ptr(dinv), _ptr(work), wbytes, s), "gp2d_trtri")
-    del work, dinv
-    guard = (GUARD_DEFAULT if guard is None else guard) and variance == "ozaki"
-    if guard:   # the guard's statistics from W, into the status word beside info
-        _guard_stats(A, n, ntr, npad, noise + jitter, status, dev)
-    else:       # "no guard ran": a receiving rank of the job stream keeps the default precision
-        status[1:].fill_(float("nan"))
-    pend = None
-    if not check:
-        # α (and the ozaki preparation) are enqueued before the status is read (one host sync per
-        # fit); a failed factor raises in GPFit.check(), which also applies the guard
-        pend = pending_status(status)
-    Y = _pad_obs(y, ntr, npad, bd, dev, perm)
-    alpha = torch.empty(n, dtype=torch.float64, device=dev)
-    pbytes = int(L.gp2d_potrs_workspace(n))
-    pwork = torch.empty(pbytes // 8 + 1, dtype=torch.float64, device=dev)
-    N.check(L.gp2d_potrs_inv(_ptr(A), n, n, _ptr(Y), _ptr(alpha), _ptr(pwork), pbytes, s), "gp2d_potrs_inv")
-    gp = GPFit(kernel=kernel, noise=float(noise), x=X, n_train=ntr, n_pad=npad, W=A, alpha=alpha, device=dev,
-               y=Y, perm=perm)
-    gp.extra["status_dev"] = status   # info + guard statistics on the device (the job stream broadcasts it)
-    del pwork
-    err = None
-    if variance == "ozaki":
-        # enqueued before the status is read, with the a-priori moduli count at the default
-        # precision: the fit's only host round trip is the status read below
-        if guard:
-            gp.extra["guard"] = dict(pending=True, diag_add=float(noise + jitter),
-                                     stream=torch.cuda.current_stream(dev))
-        try:
-            ozaki_prepare(gp, diag_add=float(noise + jitter))
-        except N.GP2DError as e:   # a failed factor (NaN rows) makes prepare fail too: info decides
-            err = e
-    if not check:
-        gp.pending = (pend[0], pend[1], err)
-        return gp
-    host = status.cpu()
-    _raise_fit_errors(int(host.view(torch.int32)[0].item()), err)
-    apply_guard(gp, float(host[1]), float(host[2]))
-    return gp
+    _factor_inverse(A, n, dinv, info, dev, join=check if join is None else join)
+    del dinv
+    gp, err = _finish_problem(st, A, y, noise, diag_add, status, guard, variance, check, dev)
+    return gp if not check else _settle(gp, status.cpu(), err)
 
 
 def fit_batch(problems, variance: str = "f64", jitter: float = 0.0, device=None, check: bool = True,
@@ -594,74 +642,35 @@ def fit_batch(problems, variance: str = "f64", jitter: float = 0.0, device=None,
     L = N.lib()
     s = _stream_handle(dev)
     prep = []
-    for kernel, x, y, noise in probs:
-        if variance == "ozaki" and not kernel.is_vector:
-            raise ValueError("the ozaki variance engine supports the vector families only")
-        X = _as_points(x, kernel.input_dim, dev)
-        ntr = X.shape[0]
-        if ntr < 1:
-            raise ValueError("need at least one training point")
+    for kernel, x, y, _ in probs:
+        st = _stage_problem(kernel, x, variance, dev)
         ny = y.numel() if isinstance(y, torch.Tensor) else np.asarray(y).size
-        if ny != kernel.block_dim * ntr:   # every problem's shape is checked before any GPU work
+        if ny != kernel.block_dim * st.ntr:   # every problem's shape is checked before the batch is assembled
             raise ValueError(f"problem {len(prep)}: observation vector has {ny} entries, "
-                             f"expected {kernel.block_dim * ntr}")
-        npad, n = fit_layout(kernel, ntr, variance)
-        perm = None
-        if variance == "ozaki" and ntr > 1:
-            perm, X = morton_sort(X)
-        prep.append((kernel, X, y, float(noise), ntr, npad, n, perm))
-    n = prep[0][6]
-    if any(p[6] != n for p in prep):
+                             f"expected {kernel.block_dim * st.ntr}")
+        prep.append(st)
+    n = prep[0].n
+    if any(st.n != n for st in prep):
         raise ValueError("fit_batch: every problem must have the same matrix order n")
-    if variance == "ozaki" and n >= 131072:
-        raise ValueError("the ozaki variance engine supports n < 131072")
     B = len(prep)
     A = torch.empty((B, n, n), dtype=torch.float64, device=dev)
-    for b, (kernel, X, _, noise, ntr, npad, _, _) in enumerate(prep):
-        N.check(L.gp2d_assemble(_ptr(X), ntr, npad, _ptr(X), ntr, npad, ctypes.byref(kernel.desc()),
-                                float(noise + jitter), ASSEMBLE_LOWER if kernel.is_vector else 1, _ptr(A[b]), n, s),
-                "gp2d_assemble")
+    for b, st in enumerate(prep):
+        _assemble_ky(st, probs[b][3] + jitter, A[b], dev)
     dinv = torch.empty((B, n // NB, NB, NB), dtype=torch.float64, device=dev)
     info = torch.empty(B, dtype=torch.int32, device=dev)   # gp2d_potrf_batched resets them
-    prev_join = L.gp2d_factor_join(1 if (check if join is None else join) else 0)
-    try:
+    with _factor_join(check if join is None else join):
         N.check(L.gp2d_potrf_batched(_ptr(A), n, n, n * n, B, _ptr(dinv), _ptr(info), s), "gp2d_potrf_batched")
-    finally:
-        L.gp2d_factor_join(prev_join)
     wbytes = int(L.gp2d_trtri_batched_workspace(n, B))
-    work = torch.empty(wbytes // 8 + 1, dtype=torch.float64, device=dev)
+    work = _workspace(wbytes, dev)
     N.check(L.gp2d_trtri_batched(_ptr(A), n, n, n * n, B, _ptr(dinv), _ptr(work), wbytes, s), "gp2d_trtri_batched")
     del work, dinv
-    pbytes = int(L.gp2d_potrs_workspace(n))
-    pwork = torch.empty(pbytes // 8 + 1, dtype=torch.float64, device=dev)
-    guard = (GUARD_DEFAULT if guard is None else guard) and variance == "ozaki"
+    pwork = _workspace(int(L.gp2d_potrs_workspace(n)), dev)
     statuses = torch.empty((B, 3), dtype=torch.float64, device=dev)   # status_block per problem
     fits, errs = [], []
-    for b, (kernel, X, y, noise, ntr, npad, _, perm) in enumerate(prep):
+    for b, st in enumerate(prep):
         statuses[b].view(torch.int32)[0:1].copy_(info[b:b + 1])        # a 4-byte device copy
-        if guard:
-            _guard_stats(A[b], n, ntr, npad, noise + jitter, statuses[b], dev)
-        else:
-            statuses[b, 1:].fill_(float("nan"))
-        bd = kernel.block_dim
-        Y = _pad_obs(y, ntr, npad, bd, dev, perm)
-        alpha = torch.empty(n, dtype=torch.float64, device=dev)
-        W = A[b]
-        N.check(L.gp2d_potrs_inv(_ptr(W), n, n, _ptr(Y), _ptr(alpha), _ptr(pwork), pbytes, s), "gp2d_potrs_inv")
-        gp = GPFit(kernel=kernel, noise=noise, x=X, n_train=ntr, n_pad=npad, W=W, alpha=alpha, device=dev, y=Y,
-                   perm=perm)
-        gp.extra["status_dev"] = statuses[b]
-        err = None
-        if variance == "ozaki":
-            if guard:
-                gp.extra["guard"] = dict(pending=True, diag_add=float(noise + jitter),
-                                         stream=torch.cuda.current_stream(dev))
-            try:
-                ozaki_prepare(gp, diag_add=float(noise + jitter))
-            except N.GP2DError as e:
-                err = e
-        if not check:
-            gp.pending = pending_status(statuses[b], err)
+        _, _, y, noise = probs[b]
+        gp, err = _finish_problem(st, A[b], y, noise, noise + jitter, statuses[b], guard, variance, check, dev, pwork)
         fits.append(gp)
         errs.append(err)
     del pwork
@@ -822,7 +831,7 @@ class Predictor:
             self._ozaki_workspace(gp.extra["ozaki"][2])
         else:
             self.wbytes = int(N.lib().gp2d_predict_workspace(gp.n, self.chunk, bd))
-            self.work = torch.empty(self.wbytes // 8 + 1, dtype=torch.float64, device=gp.device)
+            self.work = _workspace(self.wbytes, gp.device)
         self._grid = None   # (the caller's grid tensor, its version, Morton order, the grid in that order)
 
     def _ozaki_workspace(self, nmod: int):
@@ -836,7 +845,7 @@ class Predictor:
             if self.wnmod:   # a grown workspace: the old one may still be read by queued predicts
                 torch.cuda.synchronize(self.gp.device)
             self.work = None
-            self.work = torch.empty(self.wbytes // 8 + 1, dtype=torch.float64, device=self.gp.device)
+            self.work = _workspace(self.wbytes, self.gp.device)
             self.wnmod = int(nmod)
 
     def _grid_order(self, xg, G: torch.Tensor, reuse: bool):
@@ -920,7 +929,7 @@ class Predictor:
 
 
 def predict(gp: GPFit, xg, var_mode: str = "latent", compute_var: bool = True, chunk: int = 8192):
-    return Predictor(gp, chunk)(xg, var_mode=var_mode, compute_var=compute_var)
+    return _predictor_for(None, gp, chunk)(xg, var_mode=var_mode, compute_var=compute_var)
 
 
 def note_guard(stats: dict | None, gp: GPFit):
@@ -977,19 +986,17 @@ def krige_jobs(jobs, variance: str = "ozaki", chunk: int = 8192, var_mode: str =
     main = torch.cuda.current_stream(dev)
     it = iter(jobs)
     if fits_ahead is None:
-        first = next(it, None)
+        first, it = _peek(it)
         if first is None:
             return
-        it = itertools.chain([first], it)
         kernel, x, _, _, xg = first
         fits_ahead = auto_fits_ahead(kernel, _point_count(x, kernel.input_dim),
                                      _point_count(xg, kernel.input_dim), variance, compute_var)
     if int(fits_ahead) <= 0:
         if batch_fits is None or batch_ahead is None:
-            first = next(it, None)
+            first, it = _peek(it)
             if first is None:
                 return
-            it = itertools.chain([first], it)
             kernel, x, xg = first[0], first[1], first[4]
             ntr = _point_count(x, kernel.input_dim)
             if batch_fits is None:
@@ -1047,14 +1054,31 @@ def krige_jobs(jobs, variance: str = "ozaki", chunk: int = 8192, var_mode: str =
             gp.record_stream(main)
             if k == 1:
                 fill(1)   # the next job's fit, under this job's predict
-            if pred is None or not pred.fits(gp):
-                pred = Predictor(gp, chunk)
-            pred.gp = gp
-            out = pred(job[4], var_mode=var_mode, compute_var=compute_var, reuse_grid=True)
+            pred, out = _predict_job(pred, gp, job[4], chunk, var_mode, compute_var)
             yield out
     finally:
         if prev_sets is not None:
             N.lib().gp2d_factor_sets(prev_sets)
+
+
+def _peek(it):
+    """(the iterator's first item or None, an iterator that still yields it)."""
+    first = next(it, None)
+    return first, (it if first is None else itertools.chain([first], it))
+
+
+def _predictor_for(pred, gp: GPFit, chunk: int) -> Predictor:
+    """A job stream's predict workspace for `gp`: the previous one while it fits, else a new one."""
+    if pred is None or not pred.fits(gp):
+        pred = Predictor(gp, chunk)
+    pred.gp = gp
+    return pred
+
+
+def _predict_job(pred, gp: GPFit, xg, chunk: int, var_mode: str, compute_var: bool):
+    """One job's predict on the current stream: (the workspace to hand to the next job, (mean, var))."""
+    pred = _predictor_for(pred, gp, chunk)
+    return pred, pred(xg, var_mode=var_mode, compute_var=compute_var, reuse_grid=True)
 
 
 def _point_count(x, dim: int) -> int:
@@ -1195,10 +1219,7 @@ def _krige_jobs_batched(jobs, b, variance, chunk, var_mode, compute_var, jitter,
             if side is not None:
                 gp.ready_on(main)   # only the guard's own work: `side` may carry the next batch's fit
                 gp.record_stream(main)
-            if pred is None or not pred.fits(gp):
-                pred = Predictor(gp, chunk)
-            pred.gp = gp
-            out = pred(job[4], var_mode=var_mode, compute_var=compute_var, reuse_grid=True)
+            pred, out = _predict_job(pred, gp, job[4], chunk, var_mode, compute_var)
             if q == 0 and side is not None:   # the next batch's fit under this batch's predicts
                 nxt = next(groups, None)
                 nfits = issue(nxt, False) if nxt else None
@@ -1217,10 +1238,7 @@ def _krige_jobs_serial(jobs, variance, chunk, var_mode, compute_var, jitter, dev
         gp = fit(kernel, x, y, noise, jitter=jitter, device=dev, variance=variance, check=False)
         gp.check()   # status + accuracy guard before the predict
         note_guard(stats, gp)
-        if pred is None or not pred.fits(gp):
-            pred = Predictor(gp, chunk)
-        pred.gp = gp
-        out = pred(xg, var_mode=var_mode, compute_var=compute_var, reuse_grid=True)
+        pred, out = _predict_job(pred, gp, xg, chunk, var_mode, compute_var)
         yield out
 
 
@@ -1268,7 +1286,7 @@ def lml_device(gp: GPFit, eval_gradient: bool = False):
     desc = gp.kernel.desc()
     ng = int(L.gp2d_lml_grad_count(ctypes.byref(desc)))
     wbytes = int(L.gp2d_lml_grad_workspace(gp.n))
-    work = torch.empty(wbytes // 8 + 1, dtype=torch.float64, device=gp.device)
+    work = _workspace(wbytes, gp.device)
     g = torch.empty(ng, dtype=torch.float64, device=gp.device)
     N.check(L.gp2d_lml_grad(_ptr(gp.W), gp.n, gp.n, _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
                             ctypes.byref(desc), _ptr(g), _ptr(work), wbytes, s), "gp2d_lml_grad")
@@ -1293,7 +1311,7 @@ def kernel_grad(kernel: KernelSpec, xa, dL_dK, xb=None, device=None) -> np.ndarr
     desc = kernel.desc()
     ng = int(L.gp2d_kernel_grad_count(ctypes.byref(desc)))
     wbytes = int(L.gp2d_kernel_grad_workspace(A.shape[0], B.shape[0]))
-    work = torch.empty(wbytes // 8 + 1, dtype=torch.float64, device=dev)
+    work = _workspace(wbytes, dev)
     g = torch.empty(ng, dtype=torch.float64, device=dev)
     N.check(L.gp2d_kernel_grad(_ptr(A), A.shape[0], _ptr(B), B.shape[0], ctypes.byref(desc), _ptr(G), G.shape[1],
                                _ptr(g), _ptr(work), wbytes, _stream_handle(dev)), "gp2d_kernel_grad")
@@ -1362,10 +1380,7 @@ def spd_inverse(K, device=None, return_factor: bool = False):
     s = _stream_handle(dev)
     dinv = torch.empty((n // NB, NB, NB), dtype=torch.float64, device=dev)
     info = torch.empty(1, dtype=torch.int32, device=dev)
-    N.check(L.gp2d_potrf(_ptr(A), n, n, _ptr(dinv), _ptr(info), None, 0, s), "gp2d_potrf")
-    wbytes = int(L.gp2d_trtri_workspace(n))
-    work = torch.empty(wbytes // 8 + 1, dtype=torch.float64, device=dev)
-    N.check(L.gp2d_trtri(_ptr(A), n, n, _ptr(dinv), _ptr(work), wbytes, s), "gp2d_trtri")
+    _factor_inverse(A, n, dinv, info, dev)   # the join mode stays the caller's
     _raise_fit_errors(int(info.item()), None)
     Wt = torch.empty((n, n), dtype=torch.float64, device=dev)
     N.check(L.gp2d_transpose(_ptr(A), n, n, _ptr(Wt), s), "gp2d_transpose")

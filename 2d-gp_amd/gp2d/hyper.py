@@ -235,10 +235,7 @@ def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: flo
             except np.linalg.LinAlgError:
                 vals[i] = -np.inf
                 continue
-            if eval_gradient:
-                vals[i], grads[i] = E.log_marginal_likelihood(gp, eval_gradient=True)
-            else:
-                vals[i] = E.log_marginal_likelihood(gp)
+            _collect(i, gp, *E.lml_device(gp, eval_gradient), vals, grads)
             del gp
     else:
         dev = E._require_device(device)
@@ -250,14 +247,7 @@ def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: flo
             while len(inflight) > limit:
                 i, gp, out, g, ev = inflight.popleft()
                 ev.synchronize()
-                try:
-                    gp.check()
-                except np.linalg.LinAlgError:
-                    vals[i] = -np.inf
-                    continue
-                vals[i] = float(out.item())
-                if g is not None:
-                    grads[i] = g.cpu().numpy()
+                _collect(i, gp, out, g, vals, grads)
 
         prev_sets = E.N.lib().gp2d_factor_sets(c)   # one internal factor stream set per stream
         try:
@@ -269,6 +259,19 @@ def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: flo
     if ws > 1:
         vals, grads = allreduce_disjoint(vals, grads, device)
     return vals, (grads if eval_gradient else None)
+
+
+def _collect(i: int, gp: E.GPFit, out, g, vals: np.ndarray, grads: np.ndarray):
+    """Setting i's result from the device (engine.lml_device's out, g) into vals[i] / grads[i],
+    after the fit's deferred check: -inf for a non-positive-definite K_y."""
+    try:
+        gp.check()
+    except np.linalg.LinAlgError:
+        vals[i] = -np.inf
+        return
+    vals[i] = float(out.item())
+    if g is not None:
+        grads[i] = g.cpu().numpy()
 
 
 BATCH_MAX = 16              # config E (64 settings, N_train = 4096): 8 / 12 / 16 / 32 / 64 per batch
@@ -300,14 +303,7 @@ def _sweep_batched(kernel, x, y, settings, base, mine, jitter, device, eval_grad
         fits = E.fit_batch(problems, jitter=jitter, device=dev, check=False, join=True)
         outs = [E.lml_device(gp, eval_gradient) for gp in fits]
         for i, gp, (out, g) in zip(group, fits, outs):
-            try:
-                gp.check()
-            except np.linalg.LinAlgError:
-                vals[i] = -np.inf
-                continue
-            vals[i] = float(out.item())
-            if g is not None:
-                grads[i] = g.cpu().numpy()
+            _collect(i, gp, out, g, vals, grads)
         del fits, outs
 
 

@@ -268,9 +268,9 @@ class Krig:
                                                  E._stream_handle(dev)), "gp2d_gather_rows")
             Xd = Xs
         Y = E._pad_obs(y, ntr, npad, bd, dev, pm)
-        gp = E.GPFit(kernel=spec, noise=self.noise, x=Xd, n_train=ntr, n_pad=npad,
-                     W=torch.as_tensor(np.ascontiguousarray(W), device=dev),
-                     alpha=torch.as_tensor(np.ascontiguousarray(alpha), device=dev), device=dev, y=Y, perm=pm)
+        gp = E._make_fit(E._Staged(spec, Xd, ntr, npad, n, pm), self.noise,
+                         torch.as_tensor(np.ascontiguousarray(W), device=dev),
+                         torch.as_tensor(np.ascontiguousarray(alpha), device=dev), Y, dev)
         gp.extra["jitchol"] = float(jitchol_used)
         if self.variance == "ozaki":
             E.ozaki_prepare_guarded(gp, float(self.noise + (self.jitter + jitchol_used)))

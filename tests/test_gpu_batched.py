@@ -158,3 +158,30 @@ def test_fit_batch_single_and_mixed_kinds():
     for (kk, _, _, nz), gb in zip(probs, E.fit_batch(probs)):
         g = E.fit(kk, x, y, nz)
         assert same(gb.W, g.W) and same(gb.alpha, g.alpha)
+
+
+_ARD = E.KernelSpec(family="ard", variances=(1.3,), lengthscales=((6.0, 4.0),))
+_DF = E.KernelSpec(kind="df", l_df=5.0)
+
+
+@pytest.mark.parametrize("kernel,ntr,variance", [(_DF, n, v) for n in (1, 64, 65) for v in ("f64", "ozaki")]
+                         + [(_ARD, 100, "f64")])
+def test_fit_and_fit_batch_share_their_stages(kernel, ntr, variance):
+    """engine.fit, fit_batch of the one problem and fit_batch(check=False) + check() run the same
+    stages, so they return the same fit bit for bit, at the sizes where a stage takes another
+    path: one point (no Morton sort, perm None), one 64-point block column (256 for ozaki), 65
+    points (ragged padding) and the scalar family's own rounding of the matrix order."""
+    x, y = tracks(ntr, seed=300 + ntr)
+    y = y[:kernel.block_dim * ntr]
+    ref = E.fit(kernel, x, y, 0.0025, variance=variance)
+    (checked,) = E.fit_batch([(kernel, x, y, 0.0025)], variance=variance)
+    (deferred,) = E.fit_batch([(kernel, x, y, 0.0025)], variance=variance, check=False)
+    assert deferred.pending is not None
+    assert (ref.perm is None) == (ntr == 1 or variance == "f64")
+    for gp in (checked, deferred.check()):
+        assert gp.pending is None and gp.n_pad == ref.n_pad and gp.n == ref.n
+        assert same(gp.W, ref.W) and same(gp.alpha, ref.alpha) and same(gp.x, ref.x)
+        assert (gp.perm is None and ref.perm is None) or same(gp.perm, ref.perm)
+        if variance == "ozaki":
+            assert gp.extra["ozaki"][2:] == ref.extra["ozaki"][2:]
+            assert same(gp.extra["ozaki"][1].view(torch.int64), ref.extra["ozaki"][1].view(torch.int64))

@@ -369,6 +369,21 @@ def test_fit_batch_rejects_more_than_64_problems():
     assert E.fit_batch([]) == []
 
 
+def test_fit_argument_errors_come_before_the_device():
+    """What engine.fit / fit_batch can reject from their arguments alone is a ValueError, raised
+    before a device is asked for (which raises NativeLibraryError on a machine without one)."""
+    from gp2d import engine as E
+    k = E.KernelSpec(kind="df")
+    ard = E.KernelSpec(family="ard", variances=(1.0,), lengthscales=((5.0, 5.0),))
+    x, y = np.zeros((4, 2)), np.zeros(8)
+    with pytest.raises(ValueError, match="vector families only"):
+        E.fit(ard, x, y[:4], 0.01, variance="ozaki")
+    with pytest.raises(ValueError, match="variance must be one of"):
+        E.fit(k, x, y, 0.01, variance="bogus")
+    with pytest.raises(ValueError, match="variance must be one of"):
+        E.fit_batch([(k, x, y, 0.01)], variance="bogus")
+
+
 def test_ozaki_split_residues_of_wide_w_rows_exact():
     """The W residue kernel above 50 bits (csrc/ozaki.hpp ozaki_w_res_kernel, pw ≤ 60), emulated
     in fp64: x = xh·2^26 + xl exactly, the centred residues rh, rl by one fma each, and

@@ -15,6 +15,7 @@ Per variant: points/s, ms per job, the int8 GEMM's average launch (HIP events on
 copy's HIP-event ms per job and rate.  One JSON line per variant.
 usage: python tools/probe_recv_cost.py [--jobs 40] [--mb 235] [--mask 16,32] [--order A,B,...]"""
 import argparse
+import ctypes
 import itertools
 import json
 import os
@@ -30,6 +31,33 @@ import torch.distributed as dist  # noqa: E402
 from gp2d import comm as C  # noqa: E402
 from gp2d import data as D  # noqa: E402
 from gp2d import engine as E  # noqa: E402
+from gp2d import _native as N  # noqa: E402
+
+
+class MaskedStream:
+    """A HIP stream restricted to the CUs of mask bits [first, first + count)
+    (gp2d_stream_create_cumask; bit i lies in XCD i mod 8), usable as a torch stream
+    (`.stream`, a torch.cuda.ExternalStream); destroyed with the object."""
+
+    def __init__(self, first: int, count: int, device=None):
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        h = ctypes.c_void_p()
+        with torch.cuda.device(dev):
+            N.check(N.lib().gp2d_stream_create_cumask(int(first), int(count), ctypes.byref(h)),
+                    "gp2d_stream_create_cumask")
+        self.handle = h
+        self.stream = torch.cuda.ExternalStream(h.value, device=dev)
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value:
+            try:
+                torch.cuda.synchronize(self.stream.device)
+                N.lib().gp2d_stream_destroy(h)
+            except Exception:   # noqa: BLE001 — interpreter shutdown
+                pass
+            self.handle = None
+
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--jobs", type=int, default=40)
@@ -69,13 +97,13 @@ def run(variant, jobs):
         int(variant[len("mask"):]) if variant.startswith("mask") else 0)
     keep = []
     if R:
-        ps = E.MaskedStream(0, ncu - R, dev)
+        ps = MaskedStream(0, ncu - R, dev)
         keep.append(ps)
         pstream = ps.stream
     else:
         pstream = torch.cuda.current_stream(dev)
     if copy and R:
-        cs = E.MaskedStream(ncu - R, R, dev)
+        cs = MaskedStream(ncu - R, R, dev)
         keep.append(cs)
         cstream = cs.stream
     else:
