@@ -23,6 +23,7 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 // Tile of the whole engine: point counts are padded to 64, matrix orders to 128.
 constexpr int PT_TILE = 64;
 constexpr int NB = 128;
+constexpr int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
 void set_error(const std::string& msg);
 

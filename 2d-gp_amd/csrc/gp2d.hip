@@ -12,6 +12,7 @@
 #include "factor.hpp"
 #include "predict.hpp"
 #include "ozaki.hpp"
+#include "ozaki_host.hpp"
 #include "lml.hpp"
 #include "dfact.hpp"
 #include "order.hpp"
@@ -35,7 +36,6 @@ static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
 // ---------------------------------------------------------------- timing hooks
 struct Timing {
@@ -1154,13 +1154,39 @@ static int launch_w_res(const double* W, int64_t n, WRows ldw, const OzakiConsts
   return check_launch("ozaki_w_res_kernel");
 }
 
-int gp2d_ozaki_prepare(const double* W, int64_t n, int64_t ldw, const gp2d_kernel_t* k, int wbits, int kbits,
-                       int8_t* wres, double* rowscale, int* nmod_out, void* stream) {
+// argument checks of both preparations (bufs_ok: the a-priori paths also refuse NULL buffers)
+static int prepare_args(const gp2d_kernel_t* k, int wbits, int kbits, int64_t n, bool bufs_ok, const int* nmod_out) {
   GP2D_CHECK(validate_ozaki_kernel(k));
   GP2D_CHECK(valid_bits(wbits, kbits));
-  const int pw = ozaki_wbits(wbits), pb = ozaki_kbits(kbits);
   GP2D_REQUIRE(n % IBM == 0 && n > 0, "ozaki: n must be a positive multiple of 256");
+  GP2D_REQUIRE(bufs_ok, "ozaki: NULL buffer");
   GP2D_REQUIRE(nmod_out != nullptr, "ozaki: nmod_out is NULL");
+  return 0;
+}
+
+// Tail of both preparations: the constants of nmod moduli, the row scales (they need the modulus
+// product: finished from the data-driven path's exponents, or made here in the a-priori path's one
+// fused pass over W), the residue planes of W, the count.
+static int prepare_finish(int nmod, const gp2d_kernel_t* k, int pw, int pb, const double* W, int64_t n, WRows wr,
+                          int8_t* wres, double* rowscale, bool fused, int* nmod_out, hipStream_t s) {
+  OzakiConsts oc;
+  GP2D_CHECK(make_ozaki_consts(nmod, k, oc, pw, pb));
+  if (fused) {
+    ozaki_w_scale_kernel<<<(unsigned)n, 256, 0, s>>>(W, n, wr, pw, rowscale, nullptr, oc.M, oc.sB, 1);
+    GP2D_CHECK(check_launch("ozaki_w_scale_kernel"));
+  } else {
+    ozaki_rowscale_final_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(rowscale, n, oc.M, oc.sB);
+    GP2D_CHECK(check_launch("ozaki_rowscale_final_kernel"));
+  }
+  GP2D_CHECK(launch_w_res(W, n, wr, oc, wres, rowscale, s));
+  *nmod_out = nmod;
+  return 0;
+}
+
+int gp2d_ozaki_prepare(const double* W, int64_t n, int64_t ldw, const gp2d_kernel_t* k, int wbits, int kbits,
+                       int8_t* wres, double* rowscale, int* nmod_out, void* stream) {
+  GP2D_CHECK(prepare_args(k, wbits, kbits, n, true, nmod_out));
+  const int pw = ozaki_wbits(wbits), pb = ozaki_kbits(kbits);
   hipStream_t s = S(stream);
   double* l1 = reinterpret_cast<double*>(wres);  // scratch: the planes are written afterwards
   ozaki_w_scale_kernel<<<(unsigned)n, 256, 0, s>>>(W, n, WRows{ldw}, pw, rowscale, l1, 0.0, 0, 0);
@@ -1193,35 +1219,19 @@ int gp2d_ozaki_prepare(const double* W, int64_t n, int64_t ldw, const gp2d_kerne
   }
   const int nmod = ozaki_nmod_bits(std::log2(bmax));
   GP2D_REQUIRE(nmod > 0, "ozaki: row bound exceeds the modulus table");
-  OzakiConsts oc;
-  GP2D_CHECK(make_ozaki_consts(nmod, k, oc, pw, pb));
-  ozaki_rowscale_final_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(rowscale, n, oc.M, oc.sB);
-  GP2D_CHECK(check_launch("ozaki_rowscale_final_kernel"));
-  GP2D_CHECK(launch_w_res(W, n, WRows{ldw}, oc, wres, rowscale, s));
-  *nmod_out = nmod;
-  return 0;
+  return prepare_finish(nmod, k, pw, pb, W, n, WRows{ldw}, wres, rowscale, false, nmod_out, s);
 }
 
 static int prepare_apriori(const double* W, int64_t n, WRows wr, const gp2d_kernel_t* k, double diag_add,
                            int wbits, int kbits, int8_t* wres, double* rowscale, int* nmod_out, hipStream_t s) {
-  GP2D_CHECK(validate_ozaki_kernel(k));
-  GP2D_CHECK(valid_bits(wbits, kbits));
+  GP2D_CHECK(prepare_args(k, wbits, kbits, n, W != nullptr && wres != nullptr && rowscale != nullptr, nmod_out));
   const int pw = ozaki_wbits(wbits), pb = ozaki_kbits(kbits);
-  GP2D_REQUIRE(n % IBM == 0 && n > 0, "ozaki: n must be a positive multiple of 256");
-  GP2D_REQUIRE(W != nullptr && wres != nullptr && rowscale != nullptr, "ozaki: NULL buffer");
-  GP2D_REQUIRE(nmod_out != nullptr, "ozaki: nmod_out is NULL");
   // the a-priori count bounds the data-driven one for any fit with this K_y diagonal (no host
   // round trip); a violated bound could only come from a failed factor and is poisoned by CRT
   const int nmod = gp2d_ozaki_nmod_apriori(n, k, diag_add, pw, pb);
   GP2D_REQUIRE(nmod > 0, "ozaki: a-priori bound exceeds the modulus table");
-  OzakiConsts oc;
-  GP2D_CHECK(make_ozaki_consts(nmod, k, oc, pw, pb));
   // no L1 norms (the count is a-priori): one pass over W for the row exponents, one for the planes
-  ozaki_w_scale_kernel<<<(unsigned)n, 256, 0, s>>>(W, n, wr, pw, rowscale, nullptr, oc.M, oc.sB, 1);
-  GP2D_CHECK(check_launch("ozaki_w_scale_kernel"));
-  GP2D_CHECK(launch_w_res(W, n, wr, oc, wres, rowscale, s));
-  *nmod_out = nmod;
-  return 0;
+  return prepare_finish(nmod, k, pw, pb, W, n, wr, wres, rowscale, true, nmod_out, s);
 }
 
 int gp2d_ozaki_prepare_async(const double* W, int64_t n, int64_t ldw, const gp2d_kernel_t* k, double diag_add,
@@ -1304,60 +1314,58 @@ int gp2d_ozaki_guard_bits(double kss, double vmin, double target, int* wbits, in
 
 // ---- zero-slab skipping: K* block flags → per-B-tile slab lists (ozaki_slab_list_kernel)
 static int g_oz_skip = 1;
-// block flags of one chunk: [cp/64 grid blocks][npad/64 training blocks] bytes
-static size_t oz_flag_bytes(int64_t n, int64_t chunk) {
-  const int64_t cp = round_up(chunk < 1 ? 1 : chunk, IBN);
-  return (size_t)round_up((cp / OZ_KS_P) * (n / 2 / OZ_KS_T), 256);
-}
-// slab lists + prefix counts of one chunk (ints)
-static size_t oz_list_bytes(int64_t n, int64_t chunk) {
-  const int64_t nbj = 2 * round_up(chunk < 1 ? 1 : chunk, IBN) / IBN, ks = n / IBK;
-  return sizeof(int) * (size_t)(nbj * ks + nbj * (ks / 4 + 1));
-}
+void gp2d_ozaki_set_skip(int on) { g_oz_skip = on ? 1 : 0; }
 
-// workspace of gp2d_predict_ozaki for a fit with nmod moduli (the layout follows nmod)
-static size_t predict_ozaki_ws(int64_t n, int64_t chunk, int nm) {
-  if (nm <= 0 || n <= 0) return 0;
-  const int64_t cp = round_up(chunk < 1 ? 1 : chunk, IBN);
-  const int64_t ncols = 2 * cp;
-  return 2 * (size_t)nm * (size_t)n * (size_t)ncols                        // Bres + Cres planes
-         + sizeof(double) * ((size_t)(n / 2 / OZ_KS_T + 1) + (size_t)(n / OZ_CRT_ROWS + 1)) * ncols
-         + oz_flag_bytes(n, chunk) + oz_list_bytes(n, chunk);
+// ---- the predict workspace (inline K* planes, or planes from gp2d_ozaki_kstar): its sizes here
+// and its pointers in predict_ozaki_impl both come from OzakiWork (ozaki_host.hpp)
+size_t gp2d_predict_ozaki_workspace(int64_t n, int64_t chunk) {
+  return OzakiWork(n, chunk, ozaki_nmod_for(n), true).total;
 }
-static size_t predict_ozaki_planes_ws(int64_t n, int64_t chunk, int nm);
-
-size_t gp2d_predict_ozaki_workspace(int64_t n, int64_t chunk) { return predict_ozaki_ws(n, chunk, ozaki_nmod_for(n)); }
 
 size_t gp2d_predict_ozaki_workspace_nmod(int64_t n, int64_t chunk, int nmod) {
   if (nmod <= 0 || nmod > ozaki_nmod_for(n)) return 0;
-  return std::max(predict_ozaki_ws(n, chunk, nmod), predict_ozaki_planes_ws(n, chunk, nmod));
+  return std::max(OzakiWork(n, chunk, nmod, true).total, OzakiWork(n, chunk, nmod, false).total);
 }
 
-void gp2d_ozaki_set_skip(int on) { g_oz_skip = on ? 1 : 0; }
+size_t gp2d_predict_ozaki_planes_workspace(int64_t n, int64_t chunk) {
+  return OzakiWork(n, chunk, ozaki_nmod_for(n), false).total;
+}
 
-// ozaki_kstar_kernel with buffer stores whenever a plane (n × 2·cp bytes) is below 2 GiB
-static void launch_kstar(dim3 grid, hipStream_t s, const double* xtr, int64_t ntr, int64_t npad, const double* xg,
-                         int64_t cv, int64_t cp, const VecParams& vp, const double* alpha, const OzakiConsts& oc,
-                         int8_t* bres, double* pm, uint8_t* flags) {
-  if ((uint64_t)(2 * npad) * (uint64_t)(2 * cp) < (1ull << 31))
-    ozaki_kstar_kernel<true><<<grid, 256, 0, s>>>(xtr, ntr, npad, xg, cv, cp, vp, alpha, oc, bres, pm, flags);
+// The chunk of grid points starting at c0: valid points, points padded to whole 256-row tiles
+// per component half (B aliasing), columns, the chunk's grid points, ozaki_kstar_kernel's grid
+struct OzakiChunk {
+  int64_t cv, cp, ncols;
+  const double* xg;
+  dim3 kgrid;
+  OzakiChunk(const double* xg0, int64_t m, int64_t c0, int64_t chunk, int64_t ntr_pad, const gp2d_kernel_t* k)
+      : cv(std::min<int64_t>(chunk, m - c0)), cp(round_up(cv, IBN)), ncols(2 * cp), xg(xg0 + point_dim(k) * c0),
+        kgrid((unsigned)((ntr_pad + OZ_KS_T - 1) / OZ_KS_T), (unsigned)(cp / OZ_KS_P)) {}
+};
+
+// ozaki_kstar_kernel on chunk c, with buffer stores whenever a plane (n × 2·cp bytes) is below 2 GiB
+static int launch_kstar(const OzakiChunk& c, hipStream_t s, const double* xtr, int64_t ntr, int64_t npad,
+                        const VecParams& vp, const double* alpha, const OzakiConsts& oc, int8_t* bres, double* pm,
+                        uint8_t* flags) {
+  if ((uint64_t)(2 * npad) * (uint64_t)c.ncols < (1ull << 31))
+    ozaki_kstar_kernel<true><<<c.kgrid, 256, 0, s>>>(xtr, ntr, npad, c.xg, c.cv, c.cp, vp, alpha, oc, bres, pm, flags);
   else
-    ozaki_kstar_kernel<false><<<grid, 256, 0, s>>>(xtr, ntr, npad, xg, cv, cp, vp, alpha, oc, bres, pm, flags);
+    ozaki_kstar_kernel<false><<<c.kgrid, 256, 0, s>>>(xtr, ntr, npad, c.xg, c.cv, c.cp, vp, alpha, oc, bres, pm, flags);
+  return check_launch("ozaki_kstar_kernel");
 }
 
-// One chunked predict over the m grid points.  K* residue planes come either from the
-// inline ozaki_kstar_kernel (pre == nullptr: planes in the workspace, mean partials Σ α·K*)
-// or from gp2d_ozaki_kstar run earlier (pre: planes per chunk at pre + c·pre_stride, their
-// block flags pre_flags bytes further; the same kernel then runs mean-only, so the mean is
-// bit-identical to the inline path).  The int8 GEMMs skip the K slabs whose K* tile is all
+// One chunked predict over the m grid points, in the workspace `work` laid out by `lay`.  K*
+// residue planes come either from the inline ozaki_kstar_kernel (pre == nullptr: planes in the
+// workspace, mean partials Σ α·K*) or from gp2d_ozaki_kstar run earlier (planes and block flags
+// per chunk in pre_base as *pre lays them out; the same kernel then runs mean-only, so the mean
+// is bit-identical to the inline path).  The int8 GEMMs skip the K slabs whose K* tile is all
 // zero (exact: they add nothing); flags → slab lists per chunk in `skip` (oz_list_bytes).
 static int predict_ozaki_impl(const int8_t* wres, const double* rowscale, int nmod, int kbits, int64_t n,
                               const double* alpha, const double* xtr, int64_t ntr,
                               int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, int var_mode,
                               double noise, int compute_var, double* mean, double* var,
-                              const int64_t* out_order, int64_t chunk,
-                              int8_t* bres, uint8_t* cres, double* pm, double* P, uint8_t* flags, int* skip,
-                              const int8_t* pre, size_t pre_stride, size_t pre_flags, hipStream_t s) {
+                              const int64_t* out_order, int64_t chunk, const OzakiWork& lay, void* work,
+                              const KstarBuf* pre, const int8_t* pre_base, hipStream_t s) {
+  const auto [bres, cres, pm, P, flags, skip] = lay.at(work);
   OzakiConsts oc;
   GP2D_CHECK(make_ozaki_consts(nmod, k, oc, OZ_PW, ozaki_kbits(kbits)));   // pw is in the row scales already
   const int nm = oc.nmod;
@@ -1373,16 +1381,14 @@ static int predict_ozaki_impl(const int8_t* wres, const double* rowscale, int nm
   oc_mean_only.nmod = 0;   // mean only: K*·α without the residue planes
   int64_t ci = 0;
   for (int64_t c0 = 0; c0 < m; c0 += chunk, ++ci) {
-    const int64_t cv = std::min<int64_t>(chunk, m - c0);
-    const int64_t cp = round_up(cv, IBN);   // whole 256-row tiles per component half (B aliasing)
-    const int64_t ncols = 2 * cp;
-    const int8_t* B = pre ? pre + (size_t)ci * pre_stride : bres;
-    const uint8_t* F = pre ? reinterpret_cast<const uint8_t*>(B) + pre_flags : flags;
+    const OzakiChunk c(xg, m, c0, chunk, ntr_pad, k);
+    const int64_t cv = c.cv, cp = c.cp, ncols = c.ncols;
+    const int8_t* B = pre ? pre_base + pre->planes_at(ci) : bres;
+    const uint8_t* F = pre ? reinterpret_cast<const uint8_t*>(pre_base + pre->flags_at(ci)) : flags;
     const size_t bplane = (size_t)ncols * n;
     const bool inline_planes = compute_var && !pre;
-    launch_kstar(dim3((unsigned)nmseg, (unsigned)(cp / OZ_KS_P)), s, xtr, ntr, ntr_pad, xg + point_dim(k) * c0, cv,
-                 cp, vp, alpha, inline_planes ? oc : oc_mean_only, bres, pm, inline_planes ? flags : nullptr);
-    GP2D_CHECK(check_launch("ozaki_kstar_kernel"));
+    GP2D_CHECK(launch_kstar(c, s, xtr, ntr, ntr_pad, vp, alpha, inline_planes ? oc : oc_mean_only,
+                            pre ? nullptr : bres, pm, inline_planes ? flags : nullptr));
     const int nbj = (int)(ncols / IBN), kslabs = (int)(n / IBK);
     const bool use_skip = compute_var && g_oz_skip && kslabs <= (1 << 20);
     int* slist = skip;
@@ -1436,10 +1442,20 @@ static int predict_ozaki_impl(const int8_t* wres, const double* rowscale, int nm
   return 0;
 }
 
-// partial-sum doubles per chunk column: mean partials (max of the K*-segment and CRT-segment
-// counts) + variance partials
-static size_t ozaki_partials(int64_t n) {
-  return (size_t)std::max<int64_t>(n / 2 / OZ_KS_T + 1, n / OZ_CRT_ROWS + 1) + (size_t)(n / OZ_CRT_ROWS + 1);
+// Argument checks of both predict entry points, in their order (ptrs_ok: the planes path also
+// requires alpha and the planes).  1: no grid points, nothing to do.
+static int predict_ozaki_args(const gp2d_kernel_t* k, int64_t n, int64_t ntr_pad, int64_t chunk, int var_mode,
+                              bool ptrs_ok, int64_t m, int nmod, int kbits, const OzakiWork& lay, const void* work,
+                              size_t work_bytes) {
+  GP2D_CHECK(validate_ozaki_kernel(k));
+  GP2D_REQUIRE(n == 2 * ntr_pad && n % IBM == 0, "ozaki: n must equal 2·ntr_pad and be a multiple of 256");
+  GP2D_REQUIRE(chunk > 0 && chunk % (IBN / 2) == 0, "ozaki: chunk must be a positive multiple of 128");
+  GP2D_REQUIRE(var_mode >= 0 && var_mode <= 2, "predict: bad var_mode");
+  GP2D_REQUIRE(ptrs_ok, "ozaki_planes: alpha and the K* planes are required");
+  if (m <= 0) return 1;
+  GP2D_REQUIRE(nmod > 0 && nmod <= ozaki_nmod_for(n), "ozaki: nmod exceeds the moduli table");
+  GP2D_REQUIRE(work != nullptr && work_bytes >= lay.total, "ozaki: workspace too small");
+  return valid_bits(0, kbits);
 }
 
 int gp2d_predict_ozaki(const int8_t* wres, const double* rowscale, int nmod, int kbits, int64_t n, const double* alpha,
@@ -1447,25 +1463,11 @@ int gp2d_predict_ozaki(const int8_t* wres, const double* rowscale, int nmod, int
                        int64_t ntr, int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k,
                        int var_mode, double noise, int compute_var, double* mean, double* var,
                        const int64_t* out_order, int64_t chunk, void* work, size_t work_bytes, void* stream) {
-  GP2D_CHECK(validate_ozaki_kernel(k));
-  GP2D_REQUIRE(n == 2 * ntr_pad && n % IBM == 0, "ozaki: n must equal 2·ntr_pad and be a multiple of 256");
-  GP2D_REQUIRE(chunk > 0 && chunk % (IBN / 2) == 0, "ozaki: chunk must be a positive multiple of 128");
-  GP2D_REQUIRE(var_mode >= 0 && var_mode <= 2, "predict: bad var_mode");
-  if (m <= 0) return 0;
-  GP2D_REQUIRE(nmod > 0 && nmod <= ozaki_nmod_for(n), "ozaki: nmod exceeds the moduli table");
-  GP2D_REQUIRE(work != nullptr && work_bytes >= predict_ozaki_ws(n, chunk, nmod), "ozaki: workspace too small");
-  GP2D_CHECK(valid_bits(0, kbits));
-  const int nm = nmod;
-  const int64_t ncols_max = 2 * round_up(chunk, IBN);
-  int8_t* bres = reinterpret_cast<int8_t*>(work);
-  uint8_t* cres = reinterpret_cast<uint8_t*>(bres + (size_t)nm * n * ncols_max);
-  double* pm = reinterpret_cast<double*>(cres + (size_t)nm * n * ncols_max);
-  double* P = pm + (size_t)(n / 2 / OZ_KS_T + 1) * ncols_max;
-  uint8_t* flags = reinterpret_cast<uint8_t*>(P + (size_t)(n / OZ_CRT_ROWS + 1) * ncols_max);
-  int* skip = reinterpret_cast<int*>(flags + oz_flag_bytes(n, chunk));
+  const OzakiWork lay(n, chunk, nmod, true);
+  const int rc = predict_ozaki_args(k, n, ntr_pad, chunk, var_mode, true, m, nmod, kbits, lay, work, work_bytes);
+  if (rc != 0) return rc < 0 ? rc : 0;
   return predict_ozaki_impl(wres, rowscale, nmod, kbits, n, alpha, xtr, ntr, ntr_pad, xg, m, k, var_mode, noise,
-                            compute_var, mean, var, out_order, chunk, bres, cres, pm, P, flags, skip, nullptr, 0, 0,
-                            S(stream));
+                            compute_var, mean, var, out_order, chunk, lay, work, nullptr, nullptr, S(stream));
 }
 
 // ---- K* residue planes ahead of the fit (they depend on the points and the kernel only)
@@ -1491,8 +1493,7 @@ int gp2d_ozaki_nmod_apriori(int64_t n, const gp2d_kernel_t* k, double diag_add, 
 
 size_t gp2d_ozaki_kstar_bytes(int64_t n, int64_t m, int64_t chunk, int nmod) {
   if (n <= 0 || m <= 0 || chunk <= 0 || nmod <= 0) return 0;
-  const int64_t nchunks = (m + chunk - 1) / chunk;
-  return (size_t)nchunks * ((size_t)nmod * (size_t)n * (size_t)(2 * round_up(chunk, IBN)) + oz_flag_bytes(n, chunk));
+  return (size_t)((m + chunk - 1) / chunk) * KstarBuf(n, chunk, nmod).stride;
 }
 
 int gp2d_ozaki_kstar(const double* xtr, int64_t ntr, int64_t ntr_pad, const double* xg, int64_t m,
@@ -1510,31 +1511,15 @@ int gp2d_ozaki_kstar(const double* xtr, int64_t ntr, int64_t ntr_pad, const doub
   OzakiConsts oc;
   GP2D_CHECK(make_ozaki_consts(nmod, k, oc, OZ_PW, ozaki_kbits(kbits)));
   const VecParams vp = make_vec_params(k);
-  const int64_t nmseg = (ntr_pad + OZ_KS_T - 1) / OZ_KS_T;
-  const size_t planes = (size_t)nmod * (size_t)n * (size_t)(2 * round_up(chunk, IBN));
-  const size_t stride = planes + oz_flag_bytes(n, chunk);   // chunk: planes, then block flags
+  const KstarBuf buf(n, chunk, nmod);
   hipStream_t s = S(stream);
   int64_t ci = 0;
   for (int64_t c0 = 0; c0 < m; c0 += chunk, ++ci) {
-    const int64_t cv = std::min<int64_t>(chunk, m - c0);
-    const int64_t cp = round_up(cv, IBN);
-    int8_t* bc = bres + ci * stride;
-    launch_kstar(dim3((unsigned)nmseg, (unsigned)(cp / OZ_KS_P)), s, xtr, ntr, ntr_pad, xg + point_dim(k) * c0, cv,
-                 cp, vp, nullptr, oc, bc, nullptr, reinterpret_cast<uint8_t*>(bc + planes));
-    GP2D_CHECK(check_launch("ozaki_kstar_kernel"));
+    const OzakiChunk c(xg, m, c0, chunk, ntr_pad, k);
+    GP2D_CHECK(launch_kstar(c, s, xtr, ntr, ntr_pad, vp, nullptr, oc, bres + buf.planes_at(ci), nullptr,
+                            reinterpret_cast<uint8_t*>(bres + buf.flags_at(ci))));
   }
   return 0;
-}
-
-static size_t predict_ozaki_planes_ws(int64_t n, int64_t chunk, int nm) {
-  if (nm <= 0 || n <= 0) return 0;
-  const int64_t ncols = 2 * round_up(chunk < 1 ? 1 : chunk, IBN);
-  return (size_t)nm * (size_t)n * (size_t)ncols + sizeof(double) * ozaki_partials(n) * (size_t)ncols +
-         oz_list_bytes(n, chunk);
-}
-
-size_t gp2d_predict_ozaki_planes_workspace(int64_t n, int64_t chunk) {
-  return predict_ozaki_planes_ws(n, chunk, ozaki_nmod_for(n));
 }
 
 int gp2d_predict_ozaki_planes(const int8_t* wres, const double* rowscale, int nmod, int kbits, int64_t n,
@@ -1542,29 +1527,17 @@ int gp2d_predict_ozaki_planes(const int8_t* wres, const double* rowscale, int nm
                               int64_t m, const gp2d_kernel_t* k, int var_mode, double noise, const int8_t* bres,
                               int nmod_b, int kbits_b, double* mean, double* var, const int64_t* out_order, int64_t chunk, void* work,
                               size_t work_bytes, void* stream) {
-  GP2D_CHECK(validate_ozaki_kernel(k));
-  GP2D_REQUIRE(n == 2 * ntr_pad && n % IBM == 0, "ozaki: n must equal 2·ntr_pad and be a multiple of 256");
-  GP2D_REQUIRE(chunk > 0 && chunk % (IBN / 2) == 0, "ozaki: chunk must be a positive multiple of 128");
-  GP2D_REQUIRE(var_mode >= 0 && var_mode <= 2, "predict: bad var_mode");
-  GP2D_REQUIRE(alpha != nullptr && bres != nullptr, "ozaki_planes: alpha and the K* planes are required");
-  if (m <= 0) return 0;
-  GP2D_REQUIRE(nmod > 0 && nmod <= ozaki_nmod_for(n), "ozaki: nmod exceeds the moduli table");
-  GP2D_REQUIRE(work != nullptr && work_bytes >= predict_ozaki_planes_ws(n, chunk, nmod), "ozaki: workspace too small");
-  GP2D_CHECK(valid_bits(0, kbits));
+  const OzakiWork lay(n, chunk, nmod, false);
+  const int rc = predict_ozaki_args(k, n, ntr_pad, chunk, var_mode, alpha != nullptr && bres != nullptr, m, nmod,
+                                    kbits, lay, work, work_bytes);
+  if (rc != 0) return rc < 0 ? rc : 0;
   if (nmod > nmod_b || ozaki_kbits(kbits) != ozaki_kbits(kbits_b)) {
     set_error("ozaki_planes: the fit needs more moduli, or another K* precision, than the planes carry");
     return -3;
   }
-  const int64_t ncols_max = 2 * round_up(chunk, IBN);
-  uint8_t* cres = reinterpret_cast<uint8_t*>(work);
-  double* pm = reinterpret_cast<double*>(cres + (size_t)nmod * n * ncols_max);
-  double* P = pm + (size_t)std::max<int64_t>(n / 2 / OZ_KS_T + 1, n / OZ_CRT_ROWS + 1) * ncols_max;
-  int* skip = reinterpret_cast<int*>(P + (size_t)(n / OZ_CRT_ROWS + 1) * ncols_max);
-  const size_t planes = (size_t)nmod_b * (size_t)n * (size_t)ncols_max;
-  const size_t stride = planes + oz_flag_bytes(n, chunk);
+  const KstarBuf buf(n, chunk, nmod_b);
   return predict_ozaki_impl(wres, rowscale, nmod, kbits, n, alpha, xtr, ntr, ntr_pad, xg, m, k, var_mode, noise, 1, mean,
-                            var, out_order, chunk, nullptr, cres, pm, P, nullptr, skip, bres, stride, planes,
-                            S(stream));
+                            var, out_order, chunk, lay, work, &buf, bres, S(stream));
 }
 
 int gp2d_morton_codes(const double* pts, int64_t n, int dim, double* bbox, int64_t* codes, void* stream) {

@@ -1,0 +1,75 @@
+// ozaki_host.hpp — the two buffer layouts of the int8 (Ozaki-II) predict, as offset tables.
+// gp2d.hip takes every size it reports and every pointer it carves from here; nothing else
+// knows the layouts (the kernels in ozaki.hpp get plain pointers).
+#pragma once
+#include <algorithm>
+#include "ozaki.hpp"
+
+namespace gp2d {
+
+// block flags of one chunk: [cp/64 grid blocks][npad/64 training blocks] bytes
+constexpr size_t oz_flag_bytes(int64_t n, int64_t chunk) {
+  return (size_t)round_up((round_up(chunk < 1 ? 1 : chunk, IBN) / OZ_KS_P) * (n / 2 / OZ_KS_T), 256);
+}
+// slab lists + prefix counts of one chunk (ints)
+constexpr size_t oz_list_bytes(int64_t n, int64_t chunk) {
+  const int64_t nbj = 2 * round_up(chunk < 1 ? 1 : chunk, IBN) / IBN, ks = n / IBK;
+  return sizeof(int) * (size_t)(nbj * ks + nbj * (ks / 4 + 1));
+}
+
+// K* residue planes of a whole grid (gp2d_ozaki_kstar → gp2d_predict_ozaki_planes), chunk > 0:
+// per chunk the nmod planes (n × 2·cp_max bytes each), then the chunk's block flags
+struct KstarBuf {
+  size_t planes, flag_bytes, stride;
+  KstarBuf(int64_t n, int64_t chunk, int nmod)
+      : planes((size_t)nmod * (size_t)n * (size_t)(2 * round_up(chunk, IBN))), flag_bytes(oz_flag_bytes(n, chunk)),
+        stride(planes + flag_bytes) {}
+  size_t planes_at(int64_t ci) const { return (size_t)ci * stride; }   // byte offsets of chunk ci
+  size_t flags_at(int64_t ci) const { return (size_t)ci * stride + planes; }
+};
+
+// Workspace of one predict chunk for a fit with nmod moduli (the layout follows nmod), as byte
+// offsets: bres | cres | pm | P | flags | skip.  inline_planes (gp2d_predict_ozaki): the K* planes
+// and their flags live here; otherwise (gp2d_predict_ozaki_planes) they come from a KstarBuf and
+// both regions are empty.  No moduli or no rows: an empty workspace.
+struct OzakiWork {
+  size_t bres = 0, cres = 0, pm = 0, P = 0, flags = 0, skip = 0, total = 0;
+  constexpr OzakiWork(int64_t n, int64_t chunk, int nmod, bool inline_planes) {
+    if (nmod <= 0 || n <= 0) return;
+    const size_t ncols = (size_t)(2 * round_up(chunk < 1 ? 1 : chunk, IBN));
+    const size_t plane = (size_t)nmod * (size_t)n * ncols;
+    const size_t ks_rows = (size_t)(n / 2 / OZ_KS_T + 1);    // ozaki_kstar_kernel's segments (mean partials), + 1
+    const size_t crt_rows = (size_t)(n / OZ_CRT_ROWS + 1);   // ozaki_crt_colsq_kernel's segments (Σ V² partials), + 1
+    // The planes path sizes pm for the larger count.  Only ozaki_kstar_kernel writes pm (ks_rows − 1
+    // rows, all that predict_finalize_kernel reads), so ks_rows would do — and it is the maximum
+    // anyway, since OZ_CRT_ROWS ≥ 2·OZ_KS_T; callers allocate by the exported sizes, so it stays.
+    cres = bres + (inline_planes ? plane : 0);
+    pm = cres + plane;
+    P = pm + sizeof(double) * ncols * (inline_planes ? ks_rows : std::max(ks_rows, crt_rows));
+    flags = P + sizeof(double) * ncols * crt_rows;
+    skip = flags + (inline_planes ? oz_flag_bytes(n, chunk) : 0);
+    total = skip + oz_list_bytes(n, chunk);
+  }
+  struct Ptrs { int8_t* bres; uint8_t* cres; double* pm; double* P; uint8_t* flags; int* skip; };
+  Ptrs at(void* work) const {
+    char* w = static_cast<char*>(work);
+    return {reinterpret_cast<int8_t*>(w + bres), reinterpret_cast<uint8_t*>(w + cres), reinterpret_cast<double*>(w + pm),
+            reinterpret_cast<double*>(w + P), reinterpret_cast<uint8_t*>(w + flags), reinterpret_cast<int*>(w + skip)};
+  }
+};
+
+// regions in order without overlap (the total is the end of the last by construction), doubles on
+// 8 bytes, ints on 4, the planes' two regions empty exactly when the planes are not inline
+constexpr bool ozaki_work_ok(int64_t n, int64_t chunk, int nmod) {
+  for (int inl = 0; inl < 2; ++inl) {
+    const OzakiWork w(n, chunk, nmod, inl);
+    if (w.bres != 0 || (w.cres > w.bres) != inl || w.pm <= w.cres || w.P <= w.pm || w.flags <= w.P ||
+        w.skip < w.flags || (w.skip > w.flags) != inl || w.total <= w.skip || w.pm % 8 || w.P % 8 || w.skip % 4)
+      return false;
+  }
+  return true;
+}
+static_assert(ozaki_work_ok(256, 128, 12) && ozaki_work_ok(256, 128, 16) && ozaki_work_ok(8192, 8192, 13),
+              "OzakiWork: regions out of order, overlapping or misaligned");
+
+}  // namespace gp2d

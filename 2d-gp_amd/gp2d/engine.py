@@ -702,8 +702,7 @@ def ozaki_prepare(gp: GPFit, diag_add: float | None = None, packed: torch.Tensor
     # packed preparations use exactly it); the data-driven one only after (the worst case)
     nm = int(L.gp2d_ozaki_nmod_apriori(n, ctypes.byref(desc), float(diag_add), int(wbits), int(kbits))) \
         if diag_add is not None else 0
-    wbytes = nm * n * n if nm > 0 else int(L.gp2d_ozaki_wres_bytes(n))
-    wres = torch.empty(wbytes, dtype=torch.int8, device=gp.device)
+    wres = torch.empty(nm * n * n if nm > 0 else int(L.gp2d_ozaki_wres_bytes(n)), dtype=torch.int8, device=gp.device)
     rowscale = torch.empty(n, dtype=torch.float64, device=gp.device)
     nmod = ctypes.c_int(0)
     if packed is not None:
@@ -795,9 +794,8 @@ def ozaki_executed_fraction(kernel: KernelSpec, x, xg, noise: float, jitter: flo
     pl = kstar_planes(kernel, x, xg, noise, jitter, chunk, device=device)
     pl.event.synchronize()
     n, ntb, m, ch = pl.n, pl.n_pad // 64, pl.m, pl.chunk
-    cpm = (ch + 255) // 256 * 256
-    planes = pl.nmod * n * 2 * cpm
-    stride = planes + ((cpm // 64) * ntb + 255) // 256 * 256
+    planes = pl.nmod * n * 2 * ((ch + 255) // 256 * 256)   # nmod · n · 2·cp_max; the chunk's flags follow
+    stride = int(N.lib().gp2d_ozaki_kstar_bytes(n, ch, ch, pl.nmod))   # the bytes of exactly one chunk
     nbi = n // 256
     ke_slabs = 4 * np.arange(1, nbi + 1)          # a_lower: row block bi reads slabs < 4(bi+1)
     executed = dense = 0
@@ -902,24 +900,22 @@ class Predictor:
                     order, Gs = planes.order, planes.xg
                 else:
                     order, Gs = self._grid_order(xg, G, reuse_grid)
-            po = None if order is None else _ptr(order)
+            # what both predict calls start and end with: the fit, the points, the mode | outputs, workspace
+            fit_args = (_ptr(wres), _ptr(rowscale), nmod, kbits, gp.n, _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
+                        _ptr(Gs), m, ctypes.byref(desc), _VAR_MODES[var_mode], float(gp.noise))
+            out_args = (_ptr(mean), _ptr(var), None if order is None else _ptr(order), self.chunk, _ptr(self.work),
+                        self.wbytes)
             rc = -3
             if use_planes:
                 s = torch.cuda.current_stream(gp.device)
                 s.wait_event(planes.event)
-                rc = L.gp2d_predict_ozaki_planes(_ptr(wres), _ptr(rowscale), nmod, kbits, gp.n, _ptr(gp.alpha),
-                                                 _ptr(gp.x), gp.n_train, gp.n_pad, _ptr(Gs), m, ctypes.byref(desc),
-                                                 _VAR_MODES[var_mode], float(gp.noise), _ptr(planes.bres),
-                                                 planes.nmod, 0, _ptr(mean), _ptr(var), po, self.chunk, _ptr(self.work),
-                                                 self.wbytes, ctypes.c_void_p(s.cuda_stream))
+                rc = L.gp2d_predict_ozaki_planes(*fit_args, _ptr(planes.bres), planes.nmod, 0, *out_args,
+                                                 ctypes.c_void_p(s.cuda_stream))
                 if rc != -3:   # −3: the fit needs more moduli than the planes carry → inline K*
                     N.check(rc, "gp2d_predict_ozaki_planes")
             if rc == -3:
-                N.check(L.gp2d_predict_ozaki(_ptr(wres), _ptr(rowscale), nmod, kbits, gp.n, _ptr(gp.alpha), _ptr(gp.x),
-                                             gp.n_train, gp.n_pad, _ptr(Gs), m, ctypes.byref(desc),
-                                             _VAR_MODES[var_mode], float(gp.noise), int(bool(compute_var)),
-                                             _ptr(mean), _ptr(var), po, self.chunk, _ptr(self.work), self.wbytes,
-                                             _stream_handle(gp.device)), "gp2d_predict_ozaki")
+                N.check(L.gp2d_predict_ozaki(*fit_args, int(bool(compute_var)), *out_args, _stream_handle(gp.device)),
+                        "gp2d_predict_ozaki")
             return mean, (var if compute_var else None)
         N.check(L.gp2d_predict(_ptr(gp.W), gp.n, gp.n, _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
                                _ptr(G), m, ctypes.byref(desc), _VAR_MODES[var_mode], float(gp.noise),

@@ -309,3 +309,61 @@ def test_zero_slab_skip_spatiotemporal_exact():
                               noise=0.0025)
     idx = np.concatenate([np.arange(400), m + np.arange(400)])
     assert rel(vs[idx], vo) < 1e-10 and rel(ms[idx], mo) < 1e-10
+
+
+# ---------------------------------------------------------------- workspace layouts (csrc/ozaki_host.hpp)
+def _small_layout_case():
+    """df kernel, ℓ = 5, 100 training points (n = 256), 300 grid points in chunks of 128: two full
+    chunks and a ragged 44-point one — the smallest shape with more than one chunk and a padded tail."""
+    x, y = tracks(100, 81)
+    rng = np.random.default_rng(82)
+    xg = np.stack([rng.uniform(-5, 65, 300), rng.uniform(-5, 50, 300)], 1)
+    return E.KernelSpec(kind="df", l_df=5.0), x, y, xg
+
+
+def test_one_predictor_serves_fits_whose_workspace_layout_moves(monkeypatch):
+    """The predict workspace's layout follows the fit's moduli count.  One Predictor serves a
+    default-precision fit, the same data prepared at 60 / 50 bits (more moduli: the workspace grows
+    and every region moves), then the default fit again (its smaller layout inside the grown
+    block) — inline and through K* planes.  Every mean and variance is bit-identical to a fresh
+    Predictor's for that fit, inline and planes agree bit for bit, and the planes call of the 60 / 50
+    fit returns −3 (the planes carry the default precision) and falls back to the inline K*."""
+    ks, x, y, xg = _small_layout_case()
+    chunk = 128
+    gp_a = E.fit(ks, x, y, noise=0.0025, variance="ozaki", guard=False)
+    gp_b = E.ozaki_prepare(E.fit(ks, x, y, noise=0.0025, variance="ozaki", guard=False), wbits=60, kbits=50)
+    nm_a, nm_b = gp_a.extra["ozaki"][2], gp_b.extra["ozaki"][2]
+    assert gp_a.n == 256 and nm_b > nm_a
+    planes = E.kstar_planes(ks, x, xg, 0.0025, chunk=chunk)
+    assert planes.nmod >= nm_a
+    fresh = {id(gp): [t.cpu().numpy() for t in E.Predictor(gp, chunk)(xg)] for gp in (gp_a, gp_b)}
+    L = E.N.lib()
+    real, rcs = L.gp2d_predict_ozaki_planes, []
+
+    def recording(*a):
+        rcs.append(real(*a))
+        return rcs[-1]
+    monkeypatch.setattr(L, "gp2d_predict_ozaki_planes", recording)
+    pr = E.Predictor(gp_a, chunk)
+    sizes = []
+    for gp in (gp_a, gp_b, gp_a):
+        pr.gp = gp
+        mi, vi = (t.cpu().numpy() for t in pr(xg))
+        mp, vp = (t.cpu().numpy() for t in pr(xg, planes=planes))
+        sizes.append((pr.wnmod, pr.wbytes))
+        mf, vf = fresh[id(gp)]
+        assert np.array_equal(mi, mf) and np.array_equal(vi, vf)
+        assert np.array_equal(mp, mi) and np.array_equal(vp, vi)
+        assert np.all(np.isfinite(vi)) and np.all(vi > 0)
+    assert rcs == [0, -3, 0]
+    assert sizes[0][0] == nm_a and sizes[1] == sizes[2] and sizes[1][0] == nm_b and sizes[1][1] > sizes[0][1]
+
+
+def test_executed_fraction_of_the_small_case_is_the_recorded_one():
+    """engine.ozaki_executed_fraction reads the block flags behind each chunk's planes with the
+    stride gp2d_ozaki_kstar_bytes reports for one chunk: on the three-chunk case above it gives
+    exactly the value measured with the library and engine.py of commit b041f2f (which spelled the
+    stride out in NumPy).  No K* tile of this 60 km × 45 km case is all zero, so the value is 1
+    (test_zero_slab_skip_is_exact holds a fraction below 1 against its bounds)."""
+    ks, x, y, xg = _small_layout_case()
+    assert E.ozaki_executed_fraction(ks, x, xg, 0.0025, chunk=128) == 1.0   # measured at b041f2f

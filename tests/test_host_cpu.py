@@ -313,6 +313,42 @@ def test_factor_workspaces_cover_the_split_trtri():
     assert int(L.gp2d_potrf_inv_workspace(128)) == 0
 
 
+def test_ozaki_buffer_sizes_are_the_recorded_ones():
+    """The int8 predict's exported buffer sizes (host functions, no device needed) against values
+    recorded from the library of commit b041f2f, before the sizes came from the layout structs of
+    csrc/ozaki_host.hpp: callers allocate by them, so a layout change must not move them.  (The
+    structs' internal consistency — order, no overlap, alignment — is a static_assert there.)"""
+    from gp2d import _native as N
+    L = N.lib()
+    assert L.gp2d_ozaki_nmod(256) == 16 and L.gp2d_ozaki_nmod(8192) == 16 and L.gp2d_ozaki_nmod(32768) == 17
+    recorded = [
+        (L.gp2d_ozaki_wres_bytes, (0,), 0),
+        (L.gp2d_ozaki_wres_bytes, (256,), 1048576),
+        (L.gp2d_ozaki_wres_bytes, (8192,), 1073741824),
+        (L.gp2d_predict_ozaki_workspace, (256, 128), 4210992),
+        (L.gp2d_predict_ozaki_workspace, (256, 0), 4210992),        # chunk < 1 sizes as one tile
+        (L.gp2d_predict_ozaki_workspace, (0, 128), 0),
+        (L.gp2d_predict_ozaki_workspace, (8192, 8192), 4304716032),
+        (L.gp2d_predict_ozaki_planes_workspace, (256, 128), 2113584),
+        (L.gp2d_predict_ozaki_planes_workspace, (2048, 200), 16859464),
+        (L.gp2d_predict_ozaki_planes_workspace, (8192, 8192), 2157224192),
+        (L.gp2d_predict_ozaki_workspace_nmod, (256, 128, 12), 3162416),
+        (L.gp2d_predict_ozaki_workspace_nmod, (256, 128, 0), 0),
+        (L.gp2d_predict_ozaki_workspace_nmod, (256, 128, 17), 0),   # one past gp2d_ozaki_nmod(256)
+        (L.gp2d_predict_ozaki_workspace_nmod, (8192, 8192, 12), 3230974208),
+        (L.gp2d_predict_ozaki_workspace_nmod, (32768, 8192, 1), 1111949568),
+        (L.gp2d_ozaki_kstar_bytes, (256, 128, 128, 12), 1573120),   # exactly one chunk
+        (L.gp2d_ozaki_kstar_bytes, (256, 129, 128, 12), 3146240),   # one point into the second
+        (L.gp2d_ozaki_kstar_bytes, (256, 0, 128, 12), 0),
+        (L.gp2d_ozaki_kstar_bytes, (512, 65536, 0, 12), 0),
+        (L.gp2d_ozaki_kstar_bytes, (2048, 201, 200, 1), 2097664),
+        (L.gp2d_ozaki_kstar_bytes, (8192, 65536, 8192, 12), 12884967424),
+        (L.gp2d_ozaki_kstar_bytes, (32768, 65536, 8192, 17), 73014706176),
+    ]
+    for f, args, want in recorded:
+        assert int(f(*args)) == want, (f.__name__, args)
+
+
 def test_factor_join_mode_is_per_thread_and_restorable():
     """gp2d_factor_join (host state only, no device needed): a negative argument queries, the
     previous mode is returned, and the mode belongs to the calling thread (engine.fit sets and
