@@ -13,6 +13,7 @@
 #include "predict.hpp"
 #include "ozaki.hpp"
 #include "ozaki_host.hpp"
+#include "factor_host.hpp"
 #include "lml.hpp"
 #include "dfact.hpp"
 #include "order.hpp"
@@ -259,6 +260,8 @@ int gp2d_assemble_cols(const double* x, int64_t n, int64_t n_pad, const gp2d_ker
 }  // extern "C"
 
 // ------------------------------------------------------------------------ POTRF
+#define GP2D_EV(call) do { if ((call) != hipSuccess) { set_error(#call " failed"); return -1; } } while (0)
+
 namespace {
 // POTRF streams (a pool of sets per device, created lazily): `crit` carries the critical path
 // (block-column updates, diagonal block, panel TRSM) at the highest priority, `bulk` the
@@ -266,35 +269,28 @@ namespace {
 // (gp2d_potrf_inv).  (Hardware CU masks splitting the CUs between the streams were measured
 // slower at every split)  One factorisation enqueue at a time per set (its
 // mutex is held across potrf_impl's enqueue sequence).
-
-struct FactorStreams {
-  std::mutex mu;
-  // per device, up to GP2D_FACTOR_CTX stream sets, of which gp2d_factor_sets(k) puts k in use
-  // (default 1: every factorisation shares one set, as before the pool).  A caller stream keeps
-  // the set it was first given (sets dealt in order of first use), so with k > 1
-  // factorisations enqueued from different caller streams run concurrently on different sets
-  // — their chains interleave instead of queueing behind each other on one set of in-order
-  // streams
-  std::vector<std::vector<std::unique_ptr<struct FactorSet>>> sets;
-  std::vector<std::vector<std::pair<hipStream_t, int>>> owner;   // caller stream → its set
-};
+enum FactorEvent { EV_PAN, EV_HEAD, EV_JOIN, EV_START, EV_AUX0, EV_AUX1, EV_COUNT };
 struct FactorSet {
   std::mutex enqueue;                     // one factorisation enqueue at a time per set
   hipStream_t crit = nullptr, bulk = nullptr, aux = nullptr, inv = nullptr;
-  std::vector<hipEvent_t> ev;             // 6 fixed events
+  std::vector<hipEvent_t> ev;             // the EV_COUNT fixed events
   std::vector<hipEvent_t> blk;            // one per block column (fused inverse)
 };
+// per device, up to GP2D_FACTOR_CTX stream sets, of which gp2d_factor_sets(k) puts k in use
+// (default 1: every factorisation shares one set, as before the pool).  A caller stream keeps
+// the set it was first given (sets dealt in order of first use), so with k > 1
+// factorisations enqueued from different caller streams run concurrently on different sets
+// — their chains interleave instead of queueing behind each other on one set of in-order
+// streams
+struct FactorPool {
+  std::vector<std::unique_ptr<FactorSet>> sets;
+  std::vector<std::pair<hipStream_t, int>> owner;   // caller stream → its set
+};
+struct FactorStreams { std::mutex mu; std::vector<FactorPool> dev; };   // the pool of each device
 constexpr int GP2D_FACTOR_CTX = 4;
 FactorStreams g_fs;
 std::atomic<int> g_factor_sets{1};   // sets in use (gp2d_factor_sets); 1: every caller shares one
 thread_local int t_factor_join = 0;   // gp2d_factor_join: this thread's factorisations join on the host
-
-struct FactorCtx {
-  hipStream_t crit, bulk, aux, inv;
-  std::vector<hipEvent_t>* ev;
-  std::vector<hipEvent_t>* blk;
-  std::mutex* enqueue;
-};
 
 __global__ void stream_touch_kernel(int) {}
 
@@ -321,7 +317,7 @@ int ensure_factor_sets(std::vector<std::unique_ptr<FactorSet>>& sets, int count)
       stream_touch_kernel<<<1, 64, 0, st>>>(0);
       if (check_launch("stream_touch_kernel") != 0) return -1;
     }
-    f->ev.resize(6);
+    f->ev.resize(EV_COUNT);
     for (auto& e : f->ev)
       if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); return -1; }
     sets.push_back(std::move(f));
@@ -329,185 +325,127 @@ int ensure_factor_sets(std::vector<std::unique_ptr<FactorSet>>& sets, int count)
   return 0;
 }
 
-int factor_streams(FactorCtx& c, int nblk, hipStream_t caller) {
+// this device's pool, grown to fit (NULL: no device).  Caller holds g_fs.mu.
+FactorPool* device_pool() {
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { set_error("hipGetDevice failed"); return -1; }
+  if (hipGetDevice(&dev) != hipSuccess) { set_error("factor: no HIP device"); return nullptr; }
+  if ((int)g_fs.dev.size() <= dev) g_fs.dev.resize(dev + 1);
+  return &g_fs.dev[dev];
+}
+int factor_sets_in_use() { return std::max(1, std::min(GP2D_FACTOR_CTX, g_factor_sets.load())); }
+
+// The set of a factorisation enqueued from `caller`, with nblk block-column events: a known
+// stream keeps its set while that set is in use; a new one (or one whose set is no longer in
+// use) gets the next set in turn, remembered for up to 256 streams.
+FactorSet* factor_streams(int nblk, hipStream_t caller) {
   std::lock_guard<std::mutex> lk(g_fs.mu);
-  if ((int)g_fs.sets.size() <= dev) {
-    g_fs.sets.resize(dev + 1);
-    g_fs.owner.resize(dev + 1);
+  FactorPool* pool = device_pool();
+  if (!pool) return nullptr;
+  const int want = factor_sets_in_use();
+  int used = 0;
+  std::pair<hipStream_t, int>* mine = nullptr;
+  for (auto& pr : pool->owner) {
+    used += pr.second < want;
+    if (pr.first == caller) mine = &pr;
   }
-  auto& sets = g_fs.sets[dev];
-  auto& own = g_fs.owner[dev];
-  const int want = std::max(1, std::min(GP2D_FACTOR_CTX, g_factor_sets.load()));
-  int idx = -1;
-  for (const auto& pr : own)
-    if (pr.first == caller && pr.second < want) idx = pr.second;
-  if (idx < 0) {   // a new caller stream (or one whose set is no longer in use): next set in turn
-    int used = 0;
-    for (const auto& pr : own) used += pr.second < want;
+  int idx = mine ? mine->second : -1;
+  if (idx < 0 || idx >= want) {
     idx = used % want;
-    for (auto& pr : own)
-      if (pr.first == caller) pr.second = idx;
-    bool known = false;
-    for (const auto& pr : own) known = known || pr.first == caller;
-    if (!known && own.size() < 256) own.emplace_back(caller, idx);
+    if (mine) mine->second = idx;
+    else if (pool->owner.size() < 256) pool->owner.emplace_back(caller, idx);
   }
-  if (ensure_factor_sets(sets, idx + 1) != 0) return -1;
-  FactorSet& f = *sets[idx];
+  if (ensure_factor_sets(pool->sets, idx + 1) != 0) return nullptr;
+  FactorSet& f = *pool->sets[idx];
   while ((int)f.blk.size() < nblk) {
     hipEvent_t e;
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); return -1; }
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); return nullptr; }
     f.blk.push_back(e);
   }
-  c.crit = f.crit;
-  c.bulk = f.bulk;
-  c.aux = f.aux;
-  c.inv = f.inv;
-  c.ev = &f.ev;
-  c.blk = &f.blk;
-  c.enqueue = &f.enqueue;
-  return 0;
+  return &f;
 }
 
-// nprob problems at A + q·sA with their diagonal inverses at dinv + q·sD (problem batch)
-int launch_panel(double* A, int64_t lda, int k, int64_t n, const double* dinv, hipStream_t s, int nprob = 1,
+// The two skinny K = 128 launches of a right-looking factorisation of the order-n matrix at A;
+// nprob problems at A + q·sA with their diagonal inverses at dinv + q·sD (problem batch).
+// In-place panel TRSM below diagonal block k:  L21 = A21 · inv(L11)ᵀ
+int launch_panel(double* A, int64_t lda, int64_t n, int k, const double* dinv, hipStream_t s, int nprob = 1,
                  int64_t sA = 0, int64_t sD = 0) {
   const int k0 = k * NB;
   const int rows = (int)(n - k0 - NB);
   if (rows <= 0) return 0;
-  // in-place panel TRSM  L21 = A21 · inv(L11)ᵀ
   double* P = A + (int64_t)(k0 + NB) * lda + k0;
   gemm_f64_panel_kernel<PNL_TRSM_R, PNL_TRSM_CB><<<dim3((unsigned)(rows / PNL_TRSM_R), (unsigned)nprob, 1), 256, 0, s>>>(
       P, lda, dinv + (int64_t)k * NB * NB, NB, P, lda, 1.0, 0.0, sA, sD, sA);
   return check_launch("gemm_f64_panel_kernel");
 }
+// A[j.., j] −= L[j.., p] · L[j, p]ᵀ: block column j receives panel p (B = the NB rows of block
+// j of the panel)
+int launch_colupdate(double* A, int64_t lda, int64_t n, int j, int p, hipStream_t s, int nprob = 1, int64_t sA = 0) {
+  const int64_t j0 = (int64_t)j * NB;
+  const double* Lp = A + j0 * lda + (int64_t)p * NB;
+  gemm_f64_panel_kernel<PNL_UPD_R, PNL_UPD_CB>
+      <<<dim3((unsigned)((n - j0) / PNL_UPD_R), (unsigned)nprob, NB / PNL_UPD_CB), 256, 0, s>>>(
+          Lp, lda, Lp, lda, A + j0 * lda + j0, lda, -1.0, 1.0, sA, sA, sA);
+  return check_launch("gemm_f64_panel_kernel");
+}
 
 // ---- TRTRI by recursive doubling over 128-blocks (in place; the diagonal blocks already hold
-// W_kk = L_kk⁻¹): at level g every pair (left = [s·2g, s·2g+g), right = [s·2g+g, s·2g+2g))
-// forms T = L[R, left]·W[left, left], then W[R, left] = −W[R, R]·T — one batched launch per
-// level and product.  T needs (nbk·128/2 + 128)² doubles.
+// W_kk = L_kk⁻¹; pairs, K-split rule and buffer sizes in factor_host.hpp): one batched launch
+// per level and product.
 //
 // The products are triangular in K (T's column block j needs k ≥ j, W21's row block i k ≤ i),
 // so a launch that is a single round of workgroups lasts as long as its longest tile, twice the
 // average: the lower levels ran at 25–33 TF/s.  In a product with at most 256
 // tiles per pair and K ≥ 512, every tile longer than 256 is cut at its middle (GemmParams::
 // ksplit): the low halves go to the destination, the high halves to T2, then add_into_kernel
-// sums them.  The decision
-// depends on the product's shape only, so every caller (gp2d_trtri, both halves of the fused
-// inverse) sums each product in the same order.
-struct TrtriPair { int Ls, Rs, Rn, count; };
-std::vector<TrtriPair> trtri_level_pairs(int nbk, int g) {
-  const int full = nbk / (2 * g);                // pairs whose right part has g blocks
-  const int rem = nbk - full * 2 * g;            // trailing blocks
-  std::vector<TrtriPair> launches;
-  if (full > 0) launches.push_back({0, g, g, full});
-  if (rem > g) launches.push_back({full * 2 * g, full * 2 * g + g, rem - g, 1});
-  return launches;
-}
-// GemmParams::ksplit (tiles with a longer K range are cut in half) for a product with kblocks ×
-// oblocks tiles per pair, 0 = no split
-int trtri_ksplit(int kblocks, int oblocks) {
-  return (kblocks >= 4 && kblocks * oblocks <= 256) ? 2 * NB : 0;
-}
-size_t trtri_split_doubles(int nbk) {   // T2: the largest high half of any split product
-  size_t m = 0;
-  for (int g = 1; g < nbk; g *= 2)
-    for (const TrtriPair& pr : trtri_level_pairs(nbk, g))
-      if (trtri_ksplit(g, pr.Rn) || trtri_ksplit(pr.Rn, g))
-        m = std::max(m, (size_t)pr.count * pr.Rn * NB * g * NB);
-  return m;
-}
-
-int add_into(double* C, int64_t ldc, int64_t sC, const double* D, int64_t ldd, int64_t sD, int M, int N, int count,
-             hipStream_t s, int nprob = 1, int64_t pC = 0, int64_t pD = 0) {
-  add_into_kernel<<<dim3((unsigned)((N + 511) / 512), (unsigned)M, (unsigned)(count * nprob)), 256, 0, s>>>(
-      C, ldc, sC, D, ldd, sD, M, N, count, pC, pD);
+// sums them.  The decision depends on the product's shape only, so every caller (gp2d_trtri, both
+// halves of the fused inverse) sums each product in the same order.
+//
+// One product of the level-g pairs `pr` of the matrix at A, K-split and summed where the shape
+// asks for it:  which = 0:  T = L[R, L] · W[L, L]   (rh × bw; W[L, L] bw × bw lower),
+//               which = 1:  W[R, L] = −W[R, R] · T  (W[R, R] rh × rh lower).
+// Problem batch: nprob problems at A + q·sA, each with its own T (+ q·pT) and T2 (+ q·pT2);
+// every problem's products are the lone launch's (the same tiles, K ranges and split sums).
+int trtri_product(int which, double* A, int64_t lda, int g, const TrtriPair& pr, double* T, double* T2, hipStream_t s,
+                  int nprob = 1, int64_t sA = 0, int64_t pT = 0, int64_t pT2 = 0) {
+  const int64_t Lo = (int64_t)pr.Ls * NB, Ro = (int64_t)pr.Rs * NB;
+  const int bw = g * NB, rh = pr.Rn * NB;
+  const int64_t stride = (int64_t)2 * g * NB * (lda + 1);   // next pair's diagonal offset
+  const int64_t tstride = (int64_t)rh * bw;                  // next pair's T
+  double* RL = A + Ro * lda + Lo;
+  GemmParams p = gemm_params();
+  if (which == 0) {
+    p.A = RL; p.lda = lda; p.sA = stride; p.pA = sA;
+    p.B = A + Lo * lda + Lo; p.ldb = lda; p.sB = stride; p.pB = sA;
+    p.C = T; p.ldc = bw; p.sC = tstride; p.pC = pT;
+    p.M = rh; p.N = bw; p.K = bw; p.b_lower = 1;
+    p.cols_first = 1;   // column block j needs k ≥ j: long-K tiles first
+    p.ksplit = trtri_ksplit(g, pr.Rn);
+  } else {
+    p.A = A + Ro * lda + Ro; p.lda = lda; p.sA = stride; p.pA = sA;
+    p.B = T; p.ldb = bw; p.sB = tstride; p.pB = pT;
+    p.C = RL; p.ldc = lda; p.sC = stride; p.pC = sA;
+    p.M = rh; p.N = bw; p.K = rh; p.a_lower = 1; p.alpha = -1.0;
+    p.rev_rows = 1;     // row block i needs k ≤ i: long-K tiles first
+    p.ksplit = trtri_ksplit(pr.Rn, g);
+  }
+  p.pC2 = pT2;
+  if (p.ksplit) { p.zcnt = pr.count; p.C2 = T2; p.ldc2 = bw; p.sC2 = tstride; }
+  GP2D_CHECK((launch_gemm<false, EPI_STORE>(p, pr.count, s, nprob)));
+  if (!p.ksplit) return 0;
+  add_into_kernel<<<dim3((unsigned)((bw + 511) / 512), (unsigned)rh, (unsigned)(pr.count * nprob)), 256, 0, s>>>(
+      p.C, p.ldc, p.sC, T2, bw, tstride, rh, bw, pr.count, p.pC, pT2);
   return check_launch("add_into_kernel");
 }
 
-// Problem batch: nprob problems at A + q·sA, each with its own T (+ q·pT) and T2 (+ q·pT2);
-// every problem's products are the lone launch's (the same tiles, K ranges and split sums).
 int trtri_levels(double* A, int64_t lda, int nbk, double* T, double* T2, hipStream_t s, int nprob = 1,
                  int64_t sA = 0, int64_t pT = 0, int64_t pT2 = 0) {
-  for (int g = 1; g < nbk; g *= 2) {
-    for (const TrtriPair& pr : trtri_level_pairs(nbk, g)) {
-      const int64_t Lo = (int64_t)pr.Ls * NB, Ro = (int64_t)pr.Rs * NB;
-      const int bw = g * NB, rh = pr.Rn * NB;
-      const int64_t stride = (int64_t)2 * g * NB * (lda + 1);  // next pair's diagonal offset
-      // T = C · WA      C = A[R, L] (rh × bw), WA = A[L, L] (bw × bw lower)
-      GemmParams p = gemm_params();
-      p.A = A + Ro * lda + Lo; p.lda = lda; p.sA = stride;
-      p.B = A + Lo * lda + Lo; p.ldb = lda; p.sB = stride;
-      p.C = T; p.ldc = bw; p.sC = (int64_t)rh * bw;
-      p.M = rh; p.N = bw; p.K = bw; p.b_lower = 1;
-      p.cols_first = 1;   // column block j needs k ≥ j: long-K tiles first
-      p.ksplit = trtri_ksplit(g, pr.Rn);
-      if (p.ksplit) { p.zcnt = pr.count; p.C2 = T2; p.ldc2 = bw; p.sC2 = (int64_t)rh * bw; }
-      p.pA = sA; p.pB = sA; p.pC = pT; p.pC2 = pT2;
-      GP2D_CHECK((launch_gemm<false, EPI_STORE>(p, pr.count, s, nprob)));
-      if (p.ksplit)
-        GP2D_CHECK(add_into(T, bw, (int64_t)rh * bw, T2, bw, (int64_t)rh * bw, rh, bw, pr.count, s, nprob, pT, pT2));
-      // A[R, L] = −WD · T     WD = A[R, R] (rh × rh lower)
-      GemmParams q = gemm_params();
-      q.A = A + Ro * lda + Ro; q.lda = lda; q.sA = stride;
-      q.B = T; q.ldb = bw; q.sB = (int64_t)rh * bw;
-      q.C = A + Ro * lda + Lo; q.ldc = lda; q.sC = stride;
-      q.M = rh; q.N = bw; q.K = rh; q.a_lower = 1; q.alpha = -1.0;
-      q.rev_rows = 1;     // row block i needs k ≤ i: long-K tiles first
-      q.ksplit = trtri_ksplit(pr.Rn, g);
-      if (q.ksplit) { q.zcnt = pr.count; q.C2 = T2; q.ldc2 = bw; q.sC2 = (int64_t)rh * bw; }
-      q.pA = sA; q.pB = pT; q.pC = sA; q.pC2 = pT2;
-      GP2D_CHECK((launch_gemm<false, EPI_STORE>(q, pr.count, s, nprob)));
-      if (q.ksplit)
-        GP2D_CHECK(add_into(A + Ro * lda + Lo, lda, stride, T2, bw, (int64_t)rh * bw, rh, bw, pr.count, s, nprob, sA,
-                            pT2));
-    }
-  }
+  for (int g = 1; g < nbk; g *= 2)
+    for (const TrtriPair& pr : trtri_level_pairs(nbk, g))
+      for (int which = 0; which < 2; ++which)
+        GP2D_CHECK(trtri_product(which, A, lda, g, pr, T, T2, s, nprob, sA, pT, pT2));
   return 0;
 }
 
-size_t trtri_t_doubles(int64_t nbk) { return (size_t)(nbk * NB / 2 + NB) * (size_t)(nbk * NB / 2 + NB); }
-
-// The fused inverse splits the top level of the recursive doubling at h (the largest power of
-// two below nb, i.e. the TRTRI's own top-level split): once block column h−1 is factored,
-// W[0:h, 0:h] (every lower level inside the left half) and the top product T = L[h:, 0:h]·W11
-// depend on final data only, so they run on `inv` under the second half of the factorisation;
-// after the last block only W22 = L22⁻¹ and W21 = −W22·T remain.  The same GEMMs on the same
-// operands as trtri_levels over all nb blocks, so the result is bit-identical to
-// gp2d_potrf + gp2d_trtri.
-int inv_top_split(int nb) { int h = 1; while (2 * h < nb) h *= 2; return h; }
-
-int inv_top_gemm(int kind, double* A, int64_t lda, int nb, double* T2, double* T3, hipStream_t st) {
-  const int h = inv_top_split(nb);
-  const int64_t Ro = (int64_t)h * NB;
-  const int bw = h * NB, rh = (nb - h) * NB;
-  GemmParams p = gemm_params();
-  if (kind == 0) {   // T2 = L[R, left] · W[left, left]
-    p.A = A + Ro * lda; p.lda = lda;
-    p.B = A; p.ldb = lda;
-    p.C = T2; p.ldc = bw;
-    p.M = rh; p.N = bw; p.K = bw; p.b_lower = 1;
-    p.cols_first = 1;
-    p.ksplit = trtri_ksplit(h, nb - h);   // as trtri_levels' top level: the same sums
-  } else {           // W[R, left] = −W[R, R] · T2
-    p.A = A + Ro * lda + Ro; p.lda = lda;
-    p.B = T2; p.ldb = bw;
-    p.C = A + Ro * lda; p.ldc = lda;
-    p.M = rh; p.N = bw; p.K = rh; p.a_lower = 1; p.alpha = -1.0;
-    p.rev_rows = 1;
-    p.ksplit = trtri_ksplit(nb - h, h);
-  }
-  if (p.ksplit) { p.zcnt = 1; p.C2 = T3; p.ldc2 = bw; p.sC2 = (int64_t)rh * bw; }
-  GP2D_CHECK((launch_gemm<false, EPI_STORE>(p, 1, st)));
-  if (p.ksplit) GP2D_CHECK(add_into(p.C, p.ldc, 0, T3, bw, 0, rh, bw, 1, st));
-  return 0;
-}
-}  // namespace
-
-#define GP2D_EV(call) do { if ((call) != hipSuccess) { set_error(#call " failed"); return -1; } } while (0)
-
-namespace {
 // Trailing-update schedule of potrf_impl: G panels per SYRK (K = 128·G) and whether the SYRK
 // is split into the next group's head and the rest.  Measured (profiles/r04_potrf_sched_ab*.jsonl,
 // engine.fit at N_train = 1024 … 16384): four panels with the split tie the pairs where the fit
@@ -515,8 +453,7 @@ namespace {
 // 61.2 vs 63.9 ms; config D: 399 vs 417 ms); eight panels (K = 1024) gain nothing over four.
 // GP2D_POTRF_G (2 | 4 | 8) / GP2D_POTRF_SPLIT override the choice (measurement only).
 struct PotrfSchedule { int G; bool split; };
-PotrfSchedule potrf_schedule(int nb) {
-  (void)nb;
+PotrfSchedule potrf_schedule() {
   PotrfSchedule ps{4, true};
   static const char* eg = std::getenv("GP2D_POTRF_G");
   static const char* es = std::getenv("GP2D_POTRF_SPLIT");
@@ -524,7 +461,79 @@ PotrfSchedule potrf_schedule(int nb) {
   if (es) ps.split = std::atoi(es) != 0;
   return ps;
 }
-}  // namespace
+
+// nprob SPD matrices of order n at A + q·sA (one: sA = 0)
+struct PotrfJob { double* A; int64_t n, lda; int nprob; int64_t sA; };
+
+// The trailing update of group P..P+g−1, enqueued once panel P+g−1 is factored on crit:
+//   bulk: once panel P+g−1 is final, columns ≥ P+g+1 ← panels P..P+g−1 in ONE K = 128·g SYRK —
+//         g = 2 halves the launches and the C read-modify-write traffic per flop of K = 128
+//         updates; g = 4 again (the tile runs 58 vs 51 TF/s at K = 512 than at 256, m = 32640,
+//         profiles/r03_syrk_k512_ab.txt) — split (`split`) into a head, the next group's g
+//         block columns, and the rest, so the next group's prefix (the chain of g−1 diagonal
+//         blocks, during which the chip would otherwise idle) waits for the head only and runs
+//         beside the rest.
+// Regions: crit/aux write block columns ≤ P+g, the head columns P+g+1..P+2g, the rest the
+// columns beyond; bulk is in order, so the rest of group q precedes the head of group q+1,
+// which covers columns it also updates.  EV_HEAD is the head's event (the whole SYRK's when
+// unsplit, or when nothing is left to update); the rest needs no event of its own.
+int potrf_trailing_update(const PotrfJob& m, int P, int g, const PotrfSchedule& ps, FactorSet& f) {
+  GP2D_EV(hipEventRecord(f.ev[EV_PAN], f.crit));
+  GP2D_EV(hipStreamWaitEvent(f.bulk, f.ev[EV_PAN], 0));
+  const int64_t n = m.n, lda = m.lda;
+  const int64_t f0 = (int64_t)(P + g + 1) * NB;
+  const int hw = (ps.split && f0 < n) ? std::min<int>(g, (int)((n - f0) / NB)) : 0;   // head block columns
+  GemmParams q = gemm_params();
+  q.lda = lda; q.ldb = lda; q.ldc = lda;
+  q.K = g * NB; q.alpha = -1.0; q.beta = 1.0;
+  q.pA = q.pB = q.pC = m.sA;
+  auto from = [&](int64_t c0) {   // the update of every row from c0 on, columns from c0 on
+    q.A = q.B = m.A + c0 * lda + (int64_t)P * NB;
+    q.C = m.A + c0 * lda + c0;
+    q.M = (int)(n - c0);
+  };
+  if (hw > 0) {   // head: block columns [P+g+1, P+g+1+hw), every row below, lower tiles
+    from(f0);
+    q.N = hw * NB; q.cyc_lower = 1; q.mask_off = 0;
+    GP2D_CHECK((launch_gemm<true, EPI_STORE>(q, 1, f.bulk, m.nprob)));
+    GP2D_EV(hipEventRecord(f.ev[EV_HEAD], f.bulk));
+    q.cyc_lower = 0;
+  }
+  const int64_t f1 = f0 + (int64_t)hw * NB;
+  if (f1 < n) {   // the rest (or, unsplit, the whole trailing matrix): lower tiles
+    from(f1);
+    q.N = q.M; q.c_lower = 1;
+    GP2D_CHECK((launch_gemm<true, EPI_STORE>(q, 1, f.bulk, m.nprob)));
+  }
+  if (hw == 0) GP2D_EV(hipEventRecord(f.ev[EV_HEAD], f.bulk));
+  return 0;
+}
+
+// The fused inverse splits the top level of the recursive doubling at h (inv_top_split): once
+// block column h−1 is factored, W[0:h, 0:h] (every lower level inside the left half) and the
+// top product T = L[h:, 0:h]·W11 depend on final data only, so they run on `inv` under the
+// second half of the factorisation; after the last block only W22 = L22⁻¹ and W21 = −W22·T
+// remain.  The same products (trtri_product) on the same operands as trtri_levels over all nb
+// blocks, so the result is bit-identical to gp2d_potrf + gp2d_trtri.
+// left half final (block column h−1 factored on crit): W11 and T = L21·W11 under the rest
+int potrf_inv_left_half(const PotrfJob& m, int h, const PotrfInvWork::Ptrs& w, FactorSet& f) {
+  GP2D_EV(hipEventRecord(f.blk[0], f.crit));
+  GP2D_EV(hipStreamWaitEvent(f.inv, f.blk[0], 0));
+  GP2D_CHECK(trtri_levels(m.A, m.lda, h, w.T1, w.T3, f.inv));
+  return trtri_product(0, m.A, m.lda, h, {0, h, (int)(m.n / NB) - h, 1}, w.T2, w.T3, f.inv);
+}
+// after the last block (crit has joined bulk): W22 = L22⁻¹ (its lower levels) and the top
+// level's W21 = −W22·T; crit then waits for `inv`
+int potrf_inv_finish(const PotrfJob& m, int h, const PotrfInvWork::Ptrs& w, FactorSet& f) {
+  const int nb = (int)(m.n / NB);
+  GP2D_EV(hipEventRecord(f.ev[EV_JOIN], f.crit));
+  GP2D_EV(hipStreamWaitEvent(f.inv, f.ev[EV_JOIN], 0));
+  GP2D_CHECK(trtri_levels(m.A + (int64_t)h * NB * (m.lda + 1), m.lda, nb - h, w.T1, w.T3, f.inv));
+  GP2D_CHECK(trtri_product(1, m.A, m.lda, h, {0, h, nb - h, 1}, w.T2, w.T3, f.inv));
+  GP2D_EV(hipEventRecord(f.ev[EV_JOIN], f.inv));
+  GP2D_EV(hipStreamWaitEvent(f.crit, f.ev[EV_JOIN], 0));
+  return 0;
+}
 
 // Right-looking blocked Cholesky (NB = 128) with look-ahead on internal streams and the
 // trailing update delayed over pairs of panels:
@@ -534,63 +543,46 @@ PotrfSchedule potrf_schedule(int nb) {
 // so the single-workgroup diagonal kernel hides under the chip-wide SYRK.  Data regions are
 // disjoint (block columns k+1, k+2 vs ≥ k+3); bulk waits for panel k+1, crit waits for the
 // pair's SYRK before it updates block column k+3.  The caller's stream is joined at both ends.
-// With Tws != NULL the factor is inverted in place on the way (gp2d_potrf_inv, inv_top_split):
-// the diagonal kernels store W_kk, the left half of the inverse and the top-level product
-// T = L21·W11 run on `inv` under the second half of the factorisation, W22 and W21 after it.
+// With `fused` the factor is inverted in place on the way (gp2d_potrf_inv; workspace pointers
+// in `w`, unused for a single block): the diagonal kernels store W_kk, the left half of the
+// inverse and the top-level product T = L21·W11 run on `inv` under the second half of the
+// factorisation, W22 and W21 after it.
 // Problem batch (nprob > 1, gp2d_potrf_batched): nprob SPD matrices at A + q·sA, their
 // diagonal inverses at dinv + q·n·128, info_dev[q]; every launch below carries all problems
 // (workgroups per problem: the diagonal kernel's one, the panel GEMMs' grid.y, the SYRK's and
 // zeroing's grid.z), so the chain's latency is paid once for the batch and each problem's
 // arithmetic is that of a lone factorisation, bit for bit.
-static int potrf_impl(double* A, int64_t n, int64_t lda, double* dinv, int* info_dev, hipStream_t s, double* Tws,
-                      int nprob = 1, int64_t sA = 0) {
+int potrf_impl(double* A, int64_t n, int64_t lda, double* dinv, int* info_dev, hipStream_t s, bool fused,
+               const PotrfInvWork::Ptrs& w = {}, int nprob = 1, int64_t sA = 0) {
   GP2D_REQUIRE(n % NB == 0 && n > 0, "potrf: n must be a positive multiple of 128");
   GP2D_REQUIRE(lda >= n && lda % 2 == 0, "potrf: lda must be >= n and even");
   GP2D_REQUIRE(dinv != nullptr, "potrf: dinv buffer is required");
-  GP2D_REQUIRE(nprob >= 1 && (nprob == 1 || (Tws == nullptr && sA >= n * lda)), "potrf: bad problem batch");
+  GP2D_REQUIRE(nprob >= 1 && (nprob == 1 || (!fused && sA >= n * lda)), "potrf: bad problem batch");
+  const PotrfJob m{A, n, lda, nprob, sA};
   const int64_t sD = n * NB;   // one problem's diagonal inverses
   const int nb = (int)(n / NB);
-  const bool fused = Tws != nullptr;
-  FactorCtx fc;
-  GP2D_CHECK(factor_streams(fc, fused ? 1 : 0, s));
+  const int h = fused ? inv_top_split(nb) : 0;
+  FactorSet* fs = factor_streams(fused ? 1 : 0, s);
+  if (!fs) return -1;
+  FactorSet& f = *fs;
   // a set's streams and events are shared by every factorisation that draws it: two host
   // threads on one set would interleave their records and waits, so its enqueue is serialised
-  std::lock_guard<std::mutex> enqueue_lock(*fc.enqueue);
-  hipStream_t sc = fc.crit, sb = fc.bulk, sa = fc.aux, si = fc.inv;
-  std::vector<hipEvent_t>& ev = *fc.ev;
-  hipEvent_t e_pan = ev[0], e_syrk = ev[1], e_join = ev[2], e_start = ev[3];
-  hipEvent_t e_auxc[2] = {ev[4], ev[5]};   // aux's first update of an even / odd block column
+  std::lock_guard<std::mutex> enqueue_lock(f.enqueue);
+  hipStream_t sc = f.crit, sb = f.bulk, sa = f.aux;
+  hipEvent_t e_join = f.ev[EV_JOIN], e_start = f.ev[EV_START];
+  hipEvent_t e_auxc[2] = {f.ev[EV_AUX0], f.ev[EV_AUX1]};   // aux's first update of an even / odd block column
   if (info_dev) GP2D_EV(hipMemsetAsync(info_dev, 0, sizeof(int) * (size_t)nprob, s));   // the call resets info
   GP2D_EV(hipEventRecord(e_join, s));
   GP2D_EV(hipStreamWaitEvent(sc, e_join, 0));
   GP2D_EV(hipStreamWaitEvent(sb, e_join, 0));
-  if (fused) GP2D_EV(hipStreamWaitEvent(si, e_join, 0));
-  const int h = fused ? inv_top_split(nb) : 0;
-  double* T1 = Tws;                                   // lower levels (one half at a time)
-  double* T2 = fused ? Tws + trtri_t_doubles(h) : nullptr;   // top-level T, (nb−h)·128 × h·128
-  double* T3 = fused ? T2 + (size_t)(nb - h) * NB * (size_t)h * NB : nullptr;   // split products' high halves
-  // A[j.., j] −= L[j.., p] · L[j, p]ᵀ: block column j receives panel p (skinny K = 128 GEMM,
-  // B = the NB rows of block j of the panel)
-  auto colupdate = [&](int j, int p, hipStream_t st) -> int {
-    const int64_t j0 = (int64_t)j * NB;
-    const double* Lp = A + j0 * lda + (int64_t)p * NB;
-    gemm_f64_panel_kernel<PNL_UPD_R, PNL_UPD_CB>
-        <<<dim3((unsigned)((n - j0) / PNL_UPD_R), (unsigned)nprob, NB / PNL_UPD_CB), 256, 0, st>>>(
-            Lp, lda, Lp, lda, A + j0 * lda + j0, lda, -1.0, 1.0, sA, sA, sA);
-    return check_launch("gemm_f64_panel_kernel");
-  };
+  if (fused) GP2D_EV(hipStreamWaitEvent(f.inv, e_join, 0));
   // diagonal block j (Cholesky + inverse) and its panel TRSM; then (fused) the inverse's
   // GEMMs whose inputs block column j completes
   auto factor = [&](int j) -> int {
     potrf_diag_kernel<<<nprob, 256, 0, sc>>>(A, lda, j * NB, dinv, info_dev, fused ? 1 : 0, sA, sD);
     GP2D_CHECK(check_launch("potrf_diag_kernel"));
-    GP2D_CHECK(launch_panel(A, lda, j, n, dinv, sc, nprob, sA, sD));
-    if (fused && nb > 1 && j == h - 1) {   // left half final: W11 and T = L21·W11 under the rest
-      GP2D_EV(hipEventRecord((*fc.blk)[0], sc));
-      GP2D_EV(hipStreamWaitEvent(si, (*fc.blk)[0], 0));
-      GP2D_CHECK(trtri_levels(A, lda, h, T1, T3, si));
-      GP2D_CHECK(inv_top_gemm(0, A, lda, nb, T2, T3, si));
-    }
+    GP2D_CHECK(launch_panel(A, lda, n, j, dinv, sc, nprob, sA, sD));
+    if (fused && nb > 1 && j == h - 1) GP2D_CHECK(potrf_inv_left_half(m, h, w, f));
     return 0;
   };
   GP2D_CHECK(factor(0));
@@ -603,18 +595,8 @@ static int potrf_impl(double* A, int64_t n, int64_t lda, double* dinv, int* info
   //   aux:  as soon as panel r is final, block columns r+2..P+g ← panel r, so each column's
   //         older panels arrive under the diagonal kernel of its predecessor (same-column
   //         updates are ordered: crit waits for aux's last update of a column before its own);
-  //   bulk: once panel P+g−1 is final, columns ≥ P+g+1 ← panels P..P+g−1 in ONE K = 128·g SYRK —
-  //         g = 2 halves the launches and the C read-modify-write traffic per flop of K = 128
-  //         updates; g = 4 again (the tile runs 58 vs 51 TF/s at K = 512 than at 256, m = 32640,
-  //         profiles/r03_syrk_k512_ab.txt) — split (`split`) into a head, the next group's g
-  //         block columns, and the rest, so the next group's prefix (the chain of g−1 diagonal
-  //         blocks, during which the chip would otherwise idle) waits for the head only and runs
-  //         beside the rest.
-  // Regions: crit/aux write block columns ≤ P+g, the head columns P+g+1..P+2g, the rest the
-  // columns beyond; bulk is in order, so the rest of group q precedes the head of group q+1,
-  // which covers columns it also updates.
-  const PotrfSchedule ps = potrf_schedule(nb);
-  hipEvent_t e_head = e_syrk;   // with split: the head's event; the rest needs no event of its own
+  //   bulk: the group's trailing update (potrf_trailing_update).
+  const PotrfSchedule ps = potrf_schedule();
   int P = 0;
   while (P + 1 < nb) {
     const int g = std::min(ps.G, nb - 1 - P);   // panels P..P+g−1, look-ahead column P+g ≤ nb−1
@@ -625,65 +607,25 @@ static int potrf_impl(double* A, int64_t n, int64_t lda, double* dinv, int* info
       if (r + 2 <= P + g) {   // aux: columns r+2.., the next one first (crit waits for it at r+1)
         GP2D_EV(hipStreamWaitEvent(sa, e_start, 0));
         for (int c = r + 2; c <= P + g; ++c) {
-          GP2D_CHECK(colupdate(c, r, sa));
+          GP2D_CHECK(launch_colupdate(A, lda, n, c, r, sa, nprob, sA));
           if (c == r + 2) GP2D_EV(hipEventRecord(e_auxc[c & 1], sa));
         }
       }
-      if (r == P + g - 1) {   // the group's panels are final: its trailing update on bulk
-        GP2D_EV(hipEventRecord(e_pan, sc));
-        GP2D_EV(hipStreamWaitEvent(sb, e_pan, 0));
-        const int64_t f0 = (int64_t)(P + g + 1) * NB;
-        if (f0 < n) {
-          const int hw = ps.split ? std::min<int>(g, (int)((n - f0) / NB)) : 0;   // head block columns
-          GemmParams q = gemm_params();
-          q.lda = lda; q.ldb = lda; q.ldc = lda;
-          q.K = g * NB; q.alpha = -1.0; q.beta = 1.0;
-          q.pA = q.pB = q.pC = sA;
-          if (hw > 0) {   // head: block columns [P+g+1, P+g+1+hw), every row below, lower tiles
-            q.A = A + f0 * lda + (int64_t)P * NB;
-            q.B = q.A;
-            q.C = A + f0 * lda + f0;
-            q.M = (int)(n - f0); q.N = hw * NB;
-            q.cyc_lower = 1; q.mask_off = 0;
-            GP2D_CHECK((launch_gemm<true, EPI_STORE>(q, 1, sb, nprob)));
-            GP2D_EV(hipEventRecord(e_head, sb));
-            q.cyc_lower = 0;
-          }
-          const int64_t f1 = f0 + (int64_t)hw * NB;
-          if (f1 < n) {   // the rest (or, unsplit, the whole trailing matrix): lower tiles
-            q.A = A + f1 * lda + (int64_t)P * NB;
-            q.B = q.A;
-            q.C = A + f1 * lda + f1;
-            q.M = (int)(n - f1); q.N = q.M; q.c_lower = 1;
-            GP2D_CHECK((launch_gemm<true, EPI_STORE>(q, 1, sb, nprob)));
-          }
-          if (hw == 0) GP2D_EV(hipEventRecord(e_head, sb));
-        } else {
-          GP2D_EV(hipEventRecord(e_head, sb));
-        }
-      }
+      if (r == P + g - 1) GP2D_CHECK(potrf_trailing_update(m, P, g, ps, f));   // the group's panels are final
       // block column r+1 ≥ P+2 received panels P..r−1 on aux (the last of them recorded as the
       // first update of batch r−1); the same-column updates must not overlap
       if (r > P) GP2D_EV(hipStreamWaitEvent(sc, e_auxc[(r + 1) & 1], 0));
-      GP2D_CHECK(colupdate(r + 1, r, sc));
+      GP2D_CHECK(launch_colupdate(A, lda, n, r + 1, r, sc, nprob, sA));
       GP2D_CHECK(factor(r + 1));
     }
     // the next group's columns P+g+1..P+2g must have received this group's head (the whole
     // SYRK when unsplit) before crit or aux update them
-    GP2D_EV(hipStreamWaitEvent(sc, e_head, 0));
+    GP2D_EV(hipStreamWaitEvent(sc, f.ev[EV_HEAD], 0));
     P += g;
   }
   GP2D_EV(hipEventRecord(e_join, sb));
   GP2D_EV(hipStreamWaitEvent(sc, e_join, 0));
-  if (fused && nb > 1) {   // W22 = L22⁻¹ (its lower levels) and the top level's W21 = −W22·T
-    GP2D_EV(hipEventRecord(e_join, sc));
-    GP2D_EV(hipStreamWaitEvent(si, e_join, 0));
-    double* A22 = A + (int64_t)h * NB * (lda + 1);
-    GP2D_CHECK(trtri_levels(A22, lda, nb - h, T1, T3, si));
-    GP2D_CHECK(inv_top_gemm(1, A, lda, nb, T2, T3, si));
-    GP2D_EV(hipEventRecord(e_join, si));
-    GP2D_EV(hipStreamWaitEvent(sc, e_join, 0));
-  }
+  if (fused && nb > 1) GP2D_CHECK(potrf_inv_finish(m, h, w, f));
   GP2D_EV(hipEventRecord(e_join, sc));
   // The caller's wait below stays pending for the whole chain.  A pending wait on a hardware
   // queue that the CP services beside crit's, aux's or bulk's slows the chain's dispatches:
@@ -696,6 +638,7 @@ static int potrf_impl(double* A, int64_t n, int64_t lda, double* dinv, int* info
   zero_upper_kernel<<<zg, 256, 0, s>>>(A, n, lda, sA);
   return check_launch("zero_upper_kernel");
 }
+}  // namespace
 
 extern "C" {
 size_t gp2d_potrf_workspace(int64_t) { return 0; }
@@ -710,34 +653,28 @@ int gp2d_factor_sets(int k) {
     // pools hand the same streams out again; a remembered mapping could put two streams of
     // one batch on the same set, where their chains would queue behind each other)
     if (k > 1)
-      for (auto& own : g_fs.owner) own.clear();
+      for (FactorPool& pool : g_fs.dev) pool.owner.clear();
   }
   return prev;
 }
 
 int gp2d_factor_warm(int nsets, void* stream) {
   GP2D_REQUIRE(nsets >= 1 && nsets <= GP2D_FACTOR_CTX, "factor_warm: nsets must be 1..4");
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { set_error("factor_warm: no HIP device"); return -1; }
+  std::lock_guard<std::mutex> lk(g_fs.mu);
+  FactorPool* pool = device_pool();
+  if (!pool) return -1;
   // the caller's stream first (the predict stream of a job stream): then the factor sets
   stream_touch_kernel<<<1, 64, 0, S(stream)>>>(0);
   GP2D_CHECK(check_launch("stream_touch_kernel"));
-  std::lock_guard<std::mutex> lk(g_fs.mu);
-  if ((int)g_fs.sets.size() <= dev) {
-    g_fs.sets.resize(dev + 1);
-    g_fs.owner.resize(dev + 1);
-  }
-  return ensure_factor_sets(g_fs.sets[dev], nsets);
+  return ensure_factor_sets(pool->sets, nsets);
 }
 
 int gp2d_factor_set_of(void* stream) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return -1;
   std::lock_guard<std::mutex> lk(g_fs.mu);
-  if ((int)g_fs.owner.size() <= dev) return -1;
-  const int want = std::max(1, std::min(GP2D_FACTOR_CTX, g_factor_sets.load()));
-  for (const auto& pr : g_fs.owner[dev])
-    if (pr.first == S(stream)) return pr.second < want ? pr.second : -1;
+  FactorPool* pool = device_pool();
+  if (!pool) return -1;
+  for (const auto& pr : pool->owner)
+    if (pr.first == S(stream)) return pr.second < factor_sets_in_use() ? pr.second : -1;
   return -1;
 }
 
@@ -748,49 +685,39 @@ int gp2d_factor_join(int host) {
 }
 
 int gp2d_potrf(double* A, int64_t n, int64_t lda, double* dinv, int* info_dev, void*, size_t, void* stream) {
-  return potrf_impl(A, n, lda, dinv, info_dev, S(stream), nullptr);
+  return potrf_impl(A, n, lda, dinv, info_dev, S(stream), false);
 }
 
-size_t gp2d_potrf_inv_workspace(int64_t n) {
-  const int nb = (int)(n / NB);
-  if (nb <= 1) return 0;
-  const int h = inv_top_split(nb);
-  return (trtri_t_doubles(h) + (size_t)(nb - h) * NB * (size_t)h * NB +
-          std::max({trtri_split_doubles(h), trtri_split_doubles(nb - h), trtri_split_doubles(nb)})) * sizeof(double);
-}
+size_t gp2d_potrf_inv_workspace(int64_t n) { return PotrfInvWork(n).total; }
 
 int gp2d_potrf_inv(double* A, int64_t n, int64_t lda, double* dinv, int* info_dev, void* work, size_t work_bytes,
                    void* stream) {
   GP2D_REQUIRE(n % NB == 0 && n > 0, "potrf_inv: n must be a positive multiple of 128");
-  if (n == NB) return potrf_impl(A, n, lda, dinv, info_dev, S(stream), A);   // no inverse GEMMs: W = dinv
-  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_potrf_inv_workspace(n), "potrf_inv: workspace too small");
-  return potrf_impl(A, n, lda, dinv, info_dev, S(stream), reinterpret_cast<double*>(work));
+  if (n == NB) return potrf_impl(A, n, lda, dinv, info_dev, S(stream), true);   // no inverse GEMMs: W = dinv
+  const PotrfInvWork w(n);
+  GP2D_REQUIRE(work != nullptr && work_bytes >= w.total, "potrf_inv: workspace too small");
+  return potrf_impl(A, n, lda, dinv, info_dev, S(stream), true, w.at(work));
 }
 
 // ------------------------------------------------------------------------ TRTRI
-size_t gp2d_trtri_workspace(int64_t n) {
-  // T buffers of the widest level: pairs × (g·NB)² doubles  ≤ n²/4 (+ dinv if not supplied,
-  // + the high halves of the K-split products)
-  const int64_t nb = n / NB;
-  size_t t = (size_t)(n / 2 + NB) * (size_t)(n / 2 + NB) * sizeof(double);
-  return t + (size_t)nb * NB * NB * sizeof(double) + trtri_split_doubles((int)nb) * sizeof(double);
-}
+// T buffers of the widest level (+ dinv if not supplied, + the high halves of the K-split products)
+size_t gp2d_trtri_workspace(int64_t n) { return TrtriWork(n, 1, true).total; }
 
 int gp2d_trtri(double* A, int64_t n, int64_t lda, const double* dinv, void* work, size_t work_bytes, void* stream) {
   GP2D_REQUIRE(n % NB == 0 && n > 0, "trtri: n must be a positive multiple of 128");
-  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_trtri_workspace(n), "trtri: workspace too small");
+  const TrtriWork lay(n, 1, true);
+  GP2D_REQUIRE(work != nullptr && work_bytes >= lay.total, "trtri: workspace too small");
   hipStream_t s = S(stream);
   const int nb = (int)(n / NB);
-  double* T = reinterpret_cast<double*>(work);
-  double* dwork = T + (size_t)(n / 2 + NB) * (size_t)(n / 2 + NB);
+  const TrtriWork::Ptrs w = lay.at(work);
   if (!dinv) {
-    trti2_diag_kernel<<<nb, 256, 0, s>>>(A, lda, dwork);
+    trti2_diag_kernel<<<nb, 256, 0, s>>>(A, lda, w.dinv);
     GP2D_CHECK(check_launch("trti2_diag_kernel"));
-    dinv = dwork;
+    dinv = w.dinv;
   }
   put_diag_blocks_kernel<<<dim3(NB * NB / 256, nb), 256, 0, s>>>(A, lda, dinv);
   GP2D_CHECK(check_launch("put_diag_blocks_kernel"));
-  return trtri_levels(A, lda, nb, T, dwork + (size_t)nb * NB * NB, s);
+  return trtri_levels(A, lda, nb, w.T, w.T2, s);
 }
 
 // ------------------------------------------------------------------------ batched factor
@@ -802,14 +729,10 @@ int gp2d_potrf_batched(double* A, int64_t n, int64_t lda, int64_t sA, int nprob,
                        void* stream) {
   GP2D_REQUIRE(nprob >= 1 && nprob <= 64, "potrf_batched: nprob must be 1..64");
   GP2D_REQUIRE(nprob == 1 || sA >= n * lda, "potrf_batched: problem stride below n·lda");
-  return potrf_impl(A, n, lda, dinv, info_dev, S(stream), nullptr, nprob, nprob > 1 ? sA : 0);
+  return potrf_impl(A, n, lda, dinv, info_dev, S(stream), false, {}, nprob, nprob > 1 ? sA : 0);
 }
 
-size_t gp2d_trtri_batched_workspace(int64_t n, int nprob) {
-  if (nprob < 1) return 0;
-  const int64_t nb = n / NB;
-  return (size_t)nprob * ((size_t)(n / 2 + NB) * (size_t)(n / 2 + NB) + trtri_split_doubles((int)nb)) * sizeof(double);
-}
+size_t gp2d_trtri_batched_workspace(int64_t n, int nprob) { return TrtriWork(n, nprob, false).total; }
 
 int gp2d_trtri_batched(double* A, int64_t n, int64_t lda, int64_t sA, int nprob, const double* dinv, void* work,
                        size_t work_bytes, void* stream) {
@@ -817,16 +740,14 @@ int gp2d_trtri_batched(double* A, int64_t n, int64_t lda, int64_t sA, int nprob,
   GP2D_REQUIRE(nprob >= 1 && nprob <= 64, "trtri_batched: nprob must be 1..64");
   GP2D_REQUIRE(nprob == 1 || sA >= n * lda, "trtri_batched: problem stride below n·lda");
   GP2D_REQUIRE(dinv != nullptr, "trtri_batched: dinv (from gp2d_potrf_batched) is required");
-  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_trtri_batched_workspace(n, nprob),
-               "trtri_batched: workspace too small");
+  const TrtriWork lay(n, nprob, false);
+  GP2D_REQUIRE(work != nullptr && work_bytes >= lay.total, "trtri_batched: workspace too small");
   hipStream_t s = S(stream);
   const int nb = (int)(n / NB);
-  const int64_t pT = (int64_t)(n / 2 + NB) * (n / 2 + NB), pT2 = (int64_t)trtri_split_doubles(nb);
-  double* T = reinterpret_cast<double*>(work);
-  double* T2 = T + (size_t)nprob * pT;
+  const TrtriWork::Ptrs w = lay.at(work);
   put_diag_blocks_kernel<<<dim3(NB * NB / 256, nb, nprob), 256, 0, s>>>(A, lda, dinv, nprob > 1 ? sA : 0, n * NB);
   GP2D_CHECK(check_launch("put_diag_blocks_kernel"));
-  return trtri_levels(A, lda, nb, T, T2, s, nprob, nprob > 1 ? sA : 0, pT, pT2);
+  return trtri_levels(A, lda, nb, w.T, w.T2, s, nprob, nprob > 1 ? sA : 0, lay.pT, lay.pT2);
 }
 
 // ------------------------------------------------------------------------ distributed factor
@@ -838,14 +759,7 @@ int gp2d_dfact_sb(void) { return DF_SB; }
 
 size_t gp2d_dfact_panel_doubles(int64_t n) { return (size_t)(n > 0 ? n : 0) * DF_SB; }
 
-// workspace layout (doubles): the DF_SBT inverted 128×128 diagonal blocks | an int status
-// word (64 B) | the head's TRTRI buffers (T, T2) | the TRTRI step's out-of-place X[s]
-// (DF_SB rows × n, at A's column positions)
-static size_t dfact_ws_dinv() { return (size_t)DF_SBT * NB * NB; }
-static size_t dfact_ws_trtri() { return trtri_t_doubles(DF_SBT) + trtri_split_doubles(DF_SBT) + 8; }
-size_t gp2d_dfact_workspace(int64_t n) {
-  return (dfact_ws_dinv() + 8 + dfact_ws_trtri() + (size_t)DF_SB * (size_t)(n > 0 ? n : 0)) * sizeof(double);
-}
+size_t gp2d_dfact_workspace(int64_t n) { return DfactWork(n).total; }   // layout: factor_host.hpp
 
 static int dfact_args(const double* A, int64_t n, int64_t lda, int s) {
   GP2D_REQUIRE(A != nullptr, "dfact: NULL matrix");
@@ -865,43 +779,29 @@ int gp2d_dfact_panel(double* A, int64_t n, int64_t lda, int s, double* panel, in
                      size_t work_bytes, void* stream) {
   GP2D_CHECK(dfact_args(A, n, lda, s));
   GP2D_REQUIRE(panel != nullptr && info_dev != nullptr, "dfact_panel: NULL panel or info");
-  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_dfact_workspace(n), "dfact_panel: workspace too small");
+  const DfactWork lay(n);
+  GP2D_REQUIRE(work != nullptr && work_bytes >= lay.total, "dfact_panel: workspace too small");
   hipStream_t st = S(stream);
   const int64_t s0 = (int64_t)s * DF_SB;
   double* As = A + s0 * lda + s0;                  // the super-column from its diagonal down
   const int64_t rows = n - s0;                     // ≥ 512
-  double* dinv = static_cast<double*>(work);       // [DF_SBT][128][128]
-  int* tmp = reinterpret_cast<int*>(dinv + dfact_ws_dinv());
-  double* T = dinv + dfact_ws_dinv() + 8;
-  double* T2 = T + trtri_t_doubles(DF_SBT);
-  GP2D_EV(hipMemsetAsync(tmp, 0, sizeof(int), st));
+  const DfactWork::Ptrs w = lay.at(work);          // w.dinv: [DF_SBT][128][128]
+  GP2D_EV(hipMemsetAsync(w.status, 0, sizeof(int), st));
   for (int j = 0; j < DF_SBT; ++j) {
-    const int64_t c0 = (int64_t)j * NB;
-    potrf_diag_kernel<<<1, 256, 0, st>>>(As, lda, (int)c0, dinv, tmp, 0);
+    potrf_diag_kernel<<<1, 256, 0, st>>>(As, lda, j * NB, w.dinv, w.status, 0);
     GP2D_CHECK(check_launch("potrf_diag_kernel"));
-    const int64_t below = rows - c0 - NB;
-    if (below <= 0) continue;
-    double* Pj = As + (c0 + NB) * lda + c0;        // sub-column j below its diagonal block
-    gemm_f64_panel_kernel<PNL_TRSM_R, PNL_TRSM_CB><<<(unsigned)(below / PNL_TRSM_R), 256, 0, st>>>(
-        Pj, lda, dinv + j * NB * NB, NB, Pj, lda, 1.0, 0.0, 0, 0, 0);
-    GP2D_CHECK(check_launch("gemm_f64_panel_kernel"));
-    for (int j2 = j + 1; j2 < DF_SBT; ++j2) {      // sub-column j2 (rows ≥ its diagonal) −= L_j · L_j[j2 rows]ᵀ
-      const int64_t r2 = (int64_t)j2 * NB;
-      const double* Lp = As + r2 * lda + c0;
-      gemm_f64_panel_kernel<PNL_UPD_R, PNL_UPD_CB>
-          <<<dim3((unsigned)((rows - r2) / PNL_UPD_R), 1, NB / PNL_UPD_CB), 256, 0, st>>>(
-              Lp, lda, Lp, lda, As + r2 * lda + r2, lda, -1.0, 1.0, 0, 0, 0);
-      GP2D_CHECK(check_launch("gemm_f64_panel_kernel"));
-    }
+    GP2D_CHECK(launch_panel(As, lda, rows, j, w.dinv, st));   // sub-column j below its diagonal block
+    for (int j2 = j + 1; j2 < DF_SBT; ++j2)        // sub-column j2 (rows ≥ its diagonal) −= L_j · L_j[j2 rows]ᵀ
+      GP2D_CHECK(launch_colupdate(As, lda, rows, j2, j, st));
   }
-  dfact_info_kernel<<<1, 64, 0, st>>>(info_dev, tmp, s0);
+  dfact_info_kernel<<<1, 64, 0, st>>>(info_dev, w.status, s0);
   GP2D_CHECK(check_launch("dfact_info_kernel"));
   GP2D_EV(hipMemcpy2DAsync(panel, DF_SB * sizeof(double), As, lda * sizeof(double), DF_SB * sizeof(double), rows,
                            hipMemcpyDeviceToDevice, st));
   // head: D_j on the diagonal, then W[R, L] = −W[R, R]·(L[R, L]·W[L, L]) level by level
-  put_diag_blocks_kernel<<<dim3(NB * NB / 256, DF_SBT), 256, 0, st>>>(panel, DF_SB, dinv);
+  put_diag_blocks_kernel<<<dim3(NB * NB / 256, DF_SBT), 256, 0, st>>>(panel, DF_SB, w.dinv);
   GP2D_CHECK(check_launch("put_diag_blocks_kernel"));
-  return trtri_levels(panel, DF_SB, DF_SBT, T, T2, st);
+  return trtri_levels(panel, DF_SB, DF_SBT, w.T, w.T2, st);
 }
 
 // first owned super-column ≥ t (rank r of P), and how many owned ones lie in [t, t_hi)
@@ -938,7 +838,8 @@ int gp2d_dfact_invstep(double* A, int64_t n, int64_t lda, int s, const double* p
   GP2D_CHECK(dfact_args(A, n, lda, s));
   GP2D_REQUIRE(panel != nullptr, "dfact_invstep: NULL panel");
   GP2D_REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, "dfact_invstep: bad rank / world size");
-  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_dfact_workspace(n), "dfact_invstep: workspace too small");
+  const DfactWork lay(n);
+  GP2D_REQUIRE(work != nullptr && work_bytes >= lay.total, "dfact_invstep: workspace too small");
   hipStream_t st = S(stream);
   const int64_t s0 = (int64_t)s * DF_SB;
   if (s % nranks == rank) {   // this rank's W column block s starts as the identity block column
@@ -950,7 +851,7 @@ int gp2d_dfact_invstep(double* A, int64_t n, int64_t lda, int s, const double* p
   if (count == 0) return 0;
   // X[s] = D_s · R[s] out of place into Xt (DF_SB × n, A's column positions; D_s lower: row
   // block i reads k < 128(i+1)), then R[t > s] −= L21 · X[s] from Xt, then Xt → X[s]
-  double* Xt = static_cast<double*>(work) + dfact_ws_dinv() + 8 + dfact_ws_trtri();
+  double* Xt = lay.at(work).Xt;
   double* Xs = A + s0 * lda;
   auto cyc = [&](GemmParams& q) { q.jgrp = DF_SBT; q.jstep = nranks; };
   {

@@ -178,7 +178,7 @@ int main() {
   EXPECT_ERR(gp2d_status_flip(nullptr, 4, nullptr));
   EXPECT(gp2d_status_flip(reinterpret_cast<int*>(buf), 0, nullptr) == 0);                      // nothing to do
   // ---- likelihood, gradients, products
-  EXPECT_ERR(gp2d_lml(buf, 100, 100, buf, buf, 10, buf, nullptr));
+  EXPECT_ERR(gp2d_lml(buf, 100, 100, buf, buf, 101, buf, nullptr));                             // nobs > n
   EXPECT_ERR(gp2d_lml_grad(buf, 256, 256, buf, buf, 100, 128, &df, buf, nullptr, 0, nullptr));
   EXPECT_ERR(gp2d_kernel_grad(buf, 10, buf, 10, &df, buf, 19, buf, nullptr, 0, nullptr));
   EXPECT_ERR(gp2d_gemm(0, -1, 4, 4, 1.0, buf, 4, buf, 4, 0.0, buf, 4, nullptr));

@@ -349,6 +349,35 @@ def test_ozaki_buffer_sizes_are_the_recorded_ones():
         assert int(f(*args)) == want, (f.__name__, args)
 
 
+def test_factor_workspace_sizes_are_the_recorded_ones():
+    """The FP64 factor's exported workspace sizes (host functions, no device needed) against values
+    recorded from the library of commit f265eba, before the sizes came from the layout structs of
+    csrc/factor_host.hpp: callers allocate by them, so a layout change must not move them.  (The
+    structs' internal consistency — order, no overlap, alignment — is a static_assert there.)"""
+    from gp2d import _native as N
+    L = N.lib()
+    # n: trtri, potrf_inv, trtri_batched(n, 1), trtri_batched(n, 3), dfact, dfact_panel_doubles,
+    #    dfact_alpha(n, 2), pack_lower_doubles
+    recorded = {
+        0: (131072, 0, 131072, 393216, 1704064, 0, 0, 0),
+        128: (425984, 0, 294912, 884736, 2228352, 65536, 8192, 16384),
+        256: (786432, 425984, 524288, 1572864, 2752640, 131072, 16384, 49152),
+        384: (1212416, 786432, 819200, 2457600, 3276928, 196608, 24576, 98304),
+        640: (2785280, 2228224, 2129920, 6389760, 4325504, 327680, 40960, 245760),
+        1024: (6422528, 5373952, 5373952, 16121856, 5898368, 524288, 65536, 589824),
+        1152: (7241728, 6422528, 6062080, 18186240, 6422656, 589824, 73728, 737280),
+        2560: (26869760, 27394048, 24248320, 72744960, 12189824, 1310720, 163840, 3440640),
+        8192: (218234880, 239206400, 209846272, 629538816, 35258496, 4194304, 524288, 34078720),
+        32768: (2483159040, 2969698304, 2449604608, 7348813824, 135921792, 16777216, 2097152, 538968064),
+    }
+    for n, want in recorded.items():
+        got = (L.gp2d_trtri_workspace(n), L.gp2d_potrf_inv_workspace(n), L.gp2d_trtri_batched_workspace(n, 1),
+               L.gp2d_trtri_batched_workspace(n, 3), L.gp2d_dfact_workspace(n), L.gp2d_dfact_panel_doubles(n),
+               L.gp2d_dfact_alpha_workspace(n, 2), L.gp2d_pack_lower_doubles(n))
+        assert tuple(int(g) for g in got) == want, n
+        assert int(L.gp2d_potrf_workspace(n)) == 0 and int(L.gp2d_trtri_batched_workspace(n, 0)) == 0, n
+
+
 def test_factor_join_mode_is_per_thread_and_restorable():
     """gp2d_factor_join (host state only, no device needed): a negative argument queries, the
     previous mode is returned, and the mode belongs to the calling thread (engine.fit sets and
