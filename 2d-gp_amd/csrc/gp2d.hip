@@ -11,6 +11,7 @@
 #include "gemm_f64.hpp"
 #include "factor.hpp"
 #include "predict.hpp"
+#include "fields.hpp"
 #include "ozaki.hpp"
 #include "ozaki_host.hpp"
 #include "factor_host.hpp"
@@ -1036,6 +1037,84 @@ int gp2d_predict(const double* W, int64_t n, int64_t ldw, const double* alpha, c
     }
     predict_finalize_kernel<<<(unsigned)((ncols + 63) / 64), 64, 0, s>>>(
         pm, nmseg, P, npseg, ncols, cp, cv, c0, m, kss, add, clip, compute_var, mean, var, nullptr);
+    GP2D_CHECK(check_launch("predict_finalize_kernel"));
+  }
+  return 0;
+}
+
+// ------------------------------------------------------- PREDICT (derived fields)
+static bool field_kernel_ok(const gp2d_kernel_t* k) {
+  return k != nullptr && is_vector_family(k) && k->kind != GP2D_KIND_SCALAR;
+}
+
+double gp2d_field_prior_var(const gp2d_kernel_t* k, int field) {
+  if (!field_kernel_ok(k) || validate_kernel(k) != 0 ||
+      (field != GP2D_FIELD_DIVERGENCE && field != GP2D_FIELD_VORTICITY))
+    return std::nan("");
+  const double w = field_weight(k, field);
+  if (w == 0.0) return 0.0;   // the field vanishes by kind (its length scale may be unset)
+  const double l = (field == GP2D_FIELD_VORTICITY) ? k->l_df : k->l_cf;
+  const double vt = (k->family == GP2D_FAMILY_VECTOR_ST) ? k->var[0] : 1.0;
+  const double l2 = l * l;
+  return vt * (8.0 * w / (l2 * l2));
+}
+
+size_t gp2d_predict_field_workspace(int64_t n, int64_t chunk) { return gp2d_predict_workspace(n, chunk, 1); }
+
+int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
+                       int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, int field,
+                       int compute_var, double* mean, double* var, int64_t chunk, void* work, size_t work_bytes,
+                       void* stream) {
+  GP2D_CHECK(validate_kernel(k));
+  GP2D_REQUIRE(field_kernel_ok(k), "predict_field: div-free, curl-free or mixed vector kernels only");
+  GP2D_REQUIRE(field == GP2D_FIELD_DIVERGENCE || field == GP2D_FIELD_VORTICITY,
+               "predict_field: field must be GP2D_FIELD_DIVERGENCE or GP2D_FIELD_VORTICITY");
+  GP2D_REQUIRE(n == 2 * ntr_pad, "predict_field: n must equal 2 × ntr_pad");
+  GP2D_REQUIRE(n % NB == 0 && n > 0, "predict_field: n must be a positive multiple of 128");
+  GP2D_REQUIRE(ntr >= 0 && ntr <= ntr_pad && ldw >= n, "predict_field: bad point count or ldw");
+  GP2D_REQUIRE(chunk > 0 && chunk % GBN == 0, "predict_field: chunk must be a positive multiple of 128");
+  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_predict_field_workspace(n, chunk),
+               "predict_field: workspace too small");
+  if (m <= 0) return 0;
+  hipStream_t s = S(stream);
+  if (field_weight(k, field) == 0.0 && k->kind != GP2D_KIND_MIXED) {
+    // div-free flow has no divergence, curl-free flow no vorticity: exact zeros, no GEMM
+    if (hipMemsetAsync(mean, 0, sizeof(double) * (size_t)m, s) != hipSuccess ||
+        (compute_var && hipMemsetAsync(var, 0, sizeof(double) * (size_t)m, s) != hipSuccess)) {
+      set_error("predict_field: hipMemsetAsync failed");
+      return -1;
+    }
+    return 0;
+  }
+  double* Bm = reinterpret_cast<double*>(work);
+  double* pm = Bm + (size_t)n * chunk;
+  double* P = pm + (size_t)(n / MEAN_SEG + 1) * chunk;
+  const double prior = gp2d_field_prior_var(k, field);
+  const FieldParams fp = make_field_params(k, field);
+  const int dim = point_dim(k);
+  const int64_t nmseg = n / MEAN_SEG, npseg = n / GBM;
+
+  for (int64_t c0 = 0; c0 < m; c0 += chunk) {
+    const int64_t cv = std::min<int64_t>(chunk, m - c0);
+    const int64_t cp = round_up(cv, GBN);
+    // cov(observations, field) for the chunk: rows = training components, cols = target points
+    assemble_field_kernel<<<dim3((unsigned)(cp / 64), (unsigned)((ntr_pad + ASM_ROWS - 1) / ASM_ROWS)), 256, 0, s>>>(
+        xtr, ntr, ntr_pad, xg + c0 * dim, cv, cp, fp, Bm);
+    GP2D_CHECK(check_launch("assemble_field_kernel"));
+    mean_part_kernel<<<dim3((unsigned)((cp + 255) / 256), (unsigned)nmseg), 256, 0, s>>>(Bm, cp, cp, alpha, pm);
+    GP2D_CHECK(check_launch("mean_part_kernel"));
+    if (compute_var) {
+      GemmParams p = gemm_params();
+      p.A = W; p.lda = ldw;
+      p.B = Bm; p.ldb = cp;
+      p.M = (int)n; p.N = (int)cp; p.K = (int)n;
+      p.a_lower = 1; p.rev_rows = 1;
+      p.P = P; p.ldp = cp;
+      GP2D_CHECK((launch_gemm<false, EPI_COLSQ>(p, 1, s)));
+    }
+    // one component of cp columns: kss = the field's prior variance, no noise, no clipping
+    predict_finalize_kernel<<<(unsigned)((cp + 63) / 64), 64, 0, s>>>(pm, nmseg, P, npseg, cp, cp, cv, c0, m, prior, 0.0,
+                                                                     0, compute_var, mean, var, nullptr);
     GP2D_CHECK(check_launch("predict_finalize_kernel"));
   }
   return 0;

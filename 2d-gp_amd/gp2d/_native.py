@@ -17,6 +17,7 @@ ABI_VERSION = 11         # GP2D_ABI_VERSION in include/gp2d.h
 FAMILY_VECTOR2D, FAMILY_ARD_RBF, FAMILY_VECTOR_ST = 0, 1, 2
 KIND_SCALAR, KIND_DIVFREE, KIND_CURLFREE, KIND_MIXED = 0, 1, 2, 3
 VAR_LATENT, VAR_NOISY, VAR_CLIPPED = 0, 1, 2
+FIELD_DIVERGENCE, FIELD_VORTICITY = 1, 2
 COMM_INT32, COMM_FLOAT64 = 2, 8
 COMM_SUM, COMM_MAX, COMM_MIN = 0, 1, 2
 
@@ -27,6 +28,7 @@ EXPORTS = (
     "gp2d_potrf_inv_workspace", "gp2d_potrf_inv", "gp2d_potrf_batched", "gp2d_trtri_batched_workspace",
     "gp2d_trtri_batched",
     "gp2d_potrs_workspace", "gp2d_potrs_inv", "gp2d_predict_workspace", "gp2d_predict",
+    "gp2d_field_prior_var", "gp2d_predict_field_workspace", "gp2d_predict_field",
     "gp2d_ozaki_nmod", "gp2d_ozaki_wres_bytes", "gp2d_ozaki_prepare", "gp2d_ozaki_prepare_async", "gp2d_ozaki_prepare_packed",
     "gp2d_ozaki_guard_workspace", "gp2d_ozaki_guard", "gp2d_ozaki_error_model", "gp2d_ozaki_guard_bits",
     "gp2d_predict_ozaki_workspace", "gp2d_predict_ozaki_workspace_nmod",
@@ -101,6 +103,9 @@ _SIGS = {
     "gp2d_potrs_inv": (_I, [_P, _I64, _I64, _P, _P, _P, _SZ, _P]),
     "gp2d_predict_workspace": (_SZ, [_I64, _I64, _I]),
     "gp2d_predict": (_I, [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _KP, _I, _D, _I, _P, _P, _I64, _P, _SZ, _P]),
+    "gp2d_field_prior_var": (_D, [_KP, _I]),
+    "gp2d_predict_field_workspace": (_SZ, [_I64, _I64]),
+    "gp2d_predict_field": (_I, [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _KP, _I, _I, _P, _P, _I64, _P, _SZ, _P]),
     "gp2d_ozaki_nmod": (_I, [_I64]),
     "gp2d_ozaki_wres_bytes": (_SZ, [_I64]),
     "gp2d_ozaki_prepare": (_I, [_P, _I64, _I64, _KP, _I, _I, _P, _P, ctypes.POINTER(_I), _P]),

@@ -175,6 +175,12 @@ class KernelSpec:
     def kdiag(self) -> float:
         return float(N.lib().gp2d_kernel_diag(ctypes.byref(self.desc())))
 
+    def field_prior_var(self, field: str) -> float:
+        """Prior variance of a derived field (FIELDS) under this kernel: Var δ = 8·w_cf/ℓ_cf⁴,
+        Var ζ = 8·w_df/ℓ_df⁴, times var_t for 'vector_st' (gp2d_field_prior_var); 0 where the
+        field vanishes by kind.  ValueError for the scalar kind and the ARD family."""
+        return float(N.lib().gp2d_field_prior_var(ctypes.byref(self.desc()), _field_code(self, field)))
+
 
 def padded_points(n: int) -> int:
     return int(N.lib().gp2d_padded_points(int(n)))
@@ -926,6 +932,56 @@ class Predictor:
 
 def predict(gp: GPFit, xg, var_mode: str = "latent", compute_var: bool = True, chunk: int = 8192):
     return _predictor_for(None, gp, chunk)(xg, var_mode=var_mode, compute_var=compute_var)
+
+
+FIELDS = ("divergence", "vorticity")
+_FIELD_CODES = {"divergence": N.FIELD_DIVERGENCE, "vorticity": N.FIELD_VORTICITY}
+
+
+def _field_code(kernel: KernelSpec, field: str) -> int:
+    """The library's code of a derived field, or ValueError for a field or kernel without one."""
+    if field not in _FIELD_CODES:
+        raise ValueError(f"field must be one of {FIELDS}")
+    if not kernel.is_vector or kernel._KINDS[kernel.kind] == N.KIND_SCALAR:
+        raise ValueError("derived fields need a div-free, curl-free or mixed vector kernel "
+                         "(the scalar kind and the ARD family have none)")
+    return _FIELD_CODES[field]
+
+
+def predict_field(gp: GPFit, xg, field: str, compute_var: bool = True, chunk: int = 8192):
+    """Posterior mean and latent variance of a derived scalar field of the fitted velocity, at the
+    points xg: (mean, var) device tensors of shape (m,), var None if not asked.
+
+    field: 'divergence' δ = ∂f1/∂x1 + ∂f2/∂x2 or 'vorticity' ζ = ∂f2/∂x1 − ∂f1/∂x2, for points
+    (x1, x2) and components (f1, f2) = the first and second half of the observations.  With
+    Krig.predict_grid's points (x, y) and components (u, v) these are ∂u/∂x + ∂v/∂y and
+    ∂v/∂x − ∂u/∂y; a caller whose points are (Y, X) with observations [v; u] gets −ζ.
+    A derivative of a GP is a GP: mean = cᵀα and var = prior − ‖W c‖² with the field's
+    cross-covariance c and prior variance (gp2d_predict_field, DESIGN.md "Derived fields").  There is no
+    noise or clipping mode: a derived field is never observed.  The divergence of a 'df' fit and
+    the vorticity of a 'cf' fit are exact zeros.
+
+    Works for fits of either variance engine — the contraction runs on the FP64 engine from the
+    fit's W; gp.x, gp.alpha and gp.W share one point order.  ValueError for the scalar kind, the
+    ARD family, and a fit without W (a job stream's receiving rank keeps only the int8 planes)."""
+    code = _field_code(gp.kernel, field)
+    if gp.W is None:
+        raise ValueError("predict_field needs the fit's factor W = L⁻¹ (this fit keeps only its int8 planes)")
+    L = N.lib()
+    G = _as_points(xg, gp.kernel.input_dim, gp.device)
+    m = G.shape[0]
+    chunk = max(NB, (int(chunk) + NB - 1) // NB * NB)
+    chunk = min(chunk, max(NB, (m + NB - 1) // NB * NB))   # no workspace beyond the points there are
+    wbytes = int(L.gp2d_predict_field_workspace(gp.n, chunk))
+    work = _workspace(wbytes, gp.device)
+    mean = torch.empty(m, dtype=torch.float64, device=gp.device)
+    var = torch.empty(m, dtype=torch.float64, device=gp.device) if compute_var else None
+    desc = gp.kernel.desc()
+    N.check(L.gp2d_predict_field(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
+                                 _ptr(G), m, ctypes.byref(desc), code, int(bool(compute_var)), _ptr(mean),
+                                 None if var is None else _ptr(var), chunk, _ptr(work), wbytes,
+                                 _stream_handle(gp.device)), "gp2d_predict_field")
+    return mean, var
 
 
 def note_guard(stats: dict | None, gp: GPFit):

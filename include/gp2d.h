@@ -179,6 +179,39 @@ int gp2d_predict(const double* W, int64_t n, int64_t ldw, const double* alpha,
                  double* mean, double* var, int64_t chunk,
                  void* work, size_t work_bytes, void* stream);
 
+/* ---- predict: divergence and vorticity of the velocity field ----------------------
+ * Posterior mean and latent variance of a derived scalar field at m points, from the fit of
+ * the velocity observations (W, alpha as for gp2d_predict).  A derivative of a GP is a GP:
+ * with points (x1, x2) and components (f1, f2) = the first and second half of the observation
+ * vector ([u…, v…] above),
+ *   GP2D_FIELD_DIVERGENCE  δ = ∂f1/∂x1 + ∂f2/∂x2,
+ *   GP2D_FIELD_VORTICITY   ζ = ∂f2/∂x1 − ∂f1/∂x2
+ * (a caller whose points are (Y, X) gets −ζ).  Their cross-covariances with the observations
+ * are the derivatives of the 2×2 SE blocks in the target point (csrc/fields.hpp, DESIGN.md
+ * "Derived fields"); only the curl-free part carries divergence and only the div-free part vorticity.
+ * Replaces the finite differences the reference's users take of its predicted grids
+ * (GP_plots.py); the reference itself computes neither field nor their variance.
+ * Kernels: VECTOR2D and VECTOR_ST of kind DIVFREE, CURLFREE or MIXED; KIND_SCALAR and the ARD
+ * family have no meaningful derived field and are refused.
+ * gp2d_field_prior_var: Var δ = 8·w_cf/ℓ_cf⁴, Var ζ = 8·w_df/ℓ_df⁴ (× var_t for VECTOR_ST), the
+ *   second derivative of the carrying part at zero lag; w_df = 1 | 0 | ratio and w_cf = 0 | 1 |
+ *   1 − ratio for DIVFREE | CURLFREE | MIXED.  Host only; NaN on bad input.
+ * gp2d_predict_field: mean = cᵀα, var = prior − ‖W c‖² per target point (m doubles each; no
+ *   noise or clipping mode: a derived field is never observed).  chunk: a positive multiple of
+ *   128; workspace gp2d_predict_field_workspace(n, chunk) = gp2d_predict_workspace(n, chunk, 1).
+ *   gp2d_predict's loop with the field's cross-covariance in place of K*; deterministic in the
+ *   same way (no atomics, fixed reduction order: results do not depend on the sharding).  Where
+ *   the field vanishes by kind (δ of DIVFREE, ζ of CURLFREE) the outputs are exact zeros.     */
+#define GP2D_FIELD_DIVERGENCE 1
+#define GP2D_FIELD_VORTICITY  2
+double gp2d_field_prior_var(const gp2d_kernel_t* k, int field);
+size_t gp2d_predict_field_workspace(int64_t n, int64_t chunk);
+int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* alpha,
+                       const double* xtr, int64_t ntr, int64_t ntr_pad,
+                       const double* xg, int64_t m, const gp2d_kernel_t* k, int field,
+                       int compute_var, double* mean, double* var, int64_t chunk,
+                       void* work, size_t work_bytes, void* stream);
+
 /* ---- predict, FP64-accurate variance on the INT8 matrix cores (Ozaki scheme II) -----
  * Same results contract as gp2d_predict (1e-10 relative parity gate) for the vector2d
  * family; the variance contraction ‖W k*‖² runs as nmod exact int8 GEMMs
