@@ -12,6 +12,7 @@
 #include "factor.hpp"
 #include "predict.hpp"
 #include "fields.hpp"
+#include "postcov.hpp"
 #include "ozaki.hpp"
 #include "ozaki_host.hpp"
 #include "factor_host.hpp"
@@ -1116,6 +1117,69 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
     predict_finalize_kernel<<<(unsigned)((cp + 63) / 64), 64, 0, s>>>(pm, nmseg, P, npseg, cp, cp, cv, c0, m, prior, 0.0,
                                                                      0, compute_var, mean, var, nullptr);
     GP2D_CHECK(check_launch("predict_finalize_kernel"));
+  }
+  return 0;
+}
+
+// ------------------------------------------------- PREDICT (joint posterior covariance)
+size_t gp2d_predict_cov_workspace(int64_t n, int64_t m) { return PredictCovWork(n, m).total; }
+
+int gp2d_predict_cov(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
+                     int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, double diag_add,
+                     double* mean, double* cov, int64_t ldc, void* work, size_t work_bytes, void* stream) {
+  GP2D_CHECK(validate_kernel(k));
+  GP2D_REQUIRE(field_kernel_ok(k), "predict_cov: div-free, curl-free or mixed vector kernels only");
+  GP2D_REQUIRE(n == 2 * ntr_pad, "predict_cov: n must equal 2 × ntr_pad");
+  GP2D_REQUIRE(n % NB == 0 && n > 0, "predict_cov: n must be a positive multiple of 128");
+  GP2D_REQUIRE(ntr >= 0 && ntr <= ntr_pad && ldw >= n, "predict_cov: bad point count or ldw");
+  GP2D_REQUIRE(m >= 0 && postcov_q(m) < (int64_t)1 << 30 && n < (int64_t)1 << 30,
+               "predict_cov: m or n out of range");
+  if (m == 0) return 0;
+  const int64_t mp = postcov_mp(m), q = postcov_q(m);
+  GP2D_REQUIRE(ldc >= q, "predict_cov: ldc must be at least q = 2·⌈m/64⌉·64");
+  const PredictCovWork lay(n, m);
+  GP2D_REQUIRE(work != nullptr && work_bytes >= lay.total, "predict_cov: workspace too small");
+  hipStream_t s = S(stream);
+  const PredictCovWork::Ptrs w = lay.at(work);
+
+  // K*ᵀ: rows = training components, columns = target components; the mean as in gp2d_predict
+  GP2D_CHECK(assemble_impl(xtr, ntr, ntr_pad, xg, m, mp, k, 0.0, 0, w.Ks, q, s));
+  const int64_t nmseg = n / MEAN_SEG;
+  mean_part_kernel<<<dim3((unsigned)((q + 255) / 256), (unsigned)nmseg), 256, 0, s>>>(w.Ks, q, q, alpha, w.pm);
+  GP2D_CHECK(check_launch("mean_part_kernel"));
+  predict_finalize_kernel<<<(unsigned)((q + 63) / 64), 64, 0, s>>>(w.pm, nmseg, nullptr, 0, q, mp, m, 0, m, 0.0, 0.0, 0,
+                                                                   0, mean, nullptr, nullptr);
+  GP2D_CHECK(check_launch("predict_finalize_kernel"));
+
+  // V = W·K*ᵀ, gp2d_predict's product stored
+  GemmParams g = gemm_params();
+  g.A = W; g.lda = ldw;
+  g.B = w.Ks; g.ldb = q;
+  g.C = w.V; g.ldc = q;
+  g.M = (int)n; g.N = (int)q; g.K = (int)n;
+  g.a_lower = 1; g.rev_rows = 1;
+  GP2D_CHECK((launch_gemm<false, EPI_STORE>(g, 1, s)));
+
+  // Σ = K(g, g) − VᵀV (+ diag_add·I), padded points identity
+  PostcovParams p;
+  p.V = w.V; p.ldv = q;
+  p.n = (int)n; p.q = (int)q;
+  p.xg = xg;
+  p.m = (int)m; p.mp = (int)mp;
+  p.vp = make_vec_params(k);
+  p.diag_add = diag_add;
+  p.C = cov; p.ldc = ldc;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(g_timing.mu);
+    if (g_timing.on) { e0 = g_timing.get(); e1 = g_timing.get(); hipEventRecord(e0, s); }
+  }
+  GP2D_CHECK(launch_postcov(p, s));
+  if (e0) {
+    std::lock_guard<std::mutex> lk(g_timing.mu);
+    hipEventRecord(e1, s);
+    g_timing.ev.push_back({e0, e1});
+    g_timing.flops.push_back(2.0 * (double)ntr * (double)(2 * m) * (double)(2 * m));  // 2N·(2m)², the lower half
   }
   return 0;
 }

@@ -1,0 +1,211 @@
+// postcov.hpp — joint posterior covariance of the velocity at the target points,
+//   Σ = K(g, g) − VᵀV,   V = W·K*ᵀ  (n × q),
+// in the padded component-major layout of K_y: q = 2·mp, mp = ⌈m/64⌉·64, rows and columns
+// [u(g_1..g_m), pad, v(g_1..g_m), pad].
+//
+// Replaces the reference's full matrix
+//   Kss = compute_K(Xs, Ys, …);  Cov = Kss − np.dot(Ks, np.dot(Ki, Ks.T))     GP_laser.py:128-129
+// (of which it keeps the diagonal, :130-131), sklearn predict(return_cov=True) and GPy
+// predict(full_cov=True).  V is gp2d_predict's own product stored instead of column-squared
+// (gemm_f64_kernel<false, EPI_STORE>, a_lower); this header holds the TN product VᵀV with the prior
+// regenerated in its epilogue, and the workspace layout of gp2d_predict_cov.
+//
+// postcov_kernel: one lower 128×128 tile of Σ per 256-thread workgroup (tri_tile, as the c_lower
+// SYRK), 4 waves as 2×2, each wave 4×4 MFMA tiles of v_mfma_f64_16x16x4_f64.  Both operands are
+// K-major: the A fragment A[i][k] = V[k][i0+i] and the B fragment B[k][j] = V[k][j0+j] are read from
+// the same kind of LDS image, gemm_f64.hpp's NN-B image [GBK][GBN+16].  Lane l of a wave reads
+// element (kk + (l>>4))·BS_NN + c + (l&15): within a 32-lane half of the ds_read_b64 that is 2 rows
+// × 16 consecutive doubles; a row is 32 consecutive dwords and the row stride 288 dwords ≡ 32
+// (mod 64), so the half covers all 64 banks once — conflict-free, for A as for B.  K runs in
+// ascending slabs of 16 through double-buffered LDS with register prefetch, one barrier per slab;
+// no atomics, one fixed order, so the result is reproducible bit for bit.
+//
+// Epilogue: element (R, C) of the tile is prior(R, C) − acc, the prior block k(g_i, g_j) from
+// vec_block_st (the assembly's device function), + diag_add where R == C; rows and columns of
+// padded points are identity.  The value is stored at (R, C) and, from the same register value,
+// at (C, R): the 4×4 (lane group, register) blocks of each MFMA tile are transposed in the wave
+// (two __shfl_xor steps) so that a lane holds 4 consecutive rows of one column and the mirror is
+// one 32-byte store, 128 contiguous bytes per column.  A diagonal tile keeps only its elements
+// with C ≤ R and mirrors those with C < R, so no element is written twice.  The q × q prior is
+// never stored or read.
+#pragma once
+#include "assemble.hpp"
+#include "factor_host.hpp"
+#include "gemm_f64.hpp"
+#include "predict.hpp"
+
+namespace gp2d {
+
+struct PostcovParams {
+  const double* V; int64_t ldv;   // n × q, row-major
+  int n, q;                       // n a multiple of 16, q of 128
+  const double* xg;               // m target points (pdim doubles each)
+  int m, mp;                      // valid and padded points per component (q = 2·mp)
+  VecParams vp;
+  double diag_add;
+  double* C; int64_t ldc;         // q × q
+};
+
+typedef double d4u __attribute__((ext_vector_type(4), aligned(8)));
+
+// the prior's entry for matrix row R and column C (component-major, mp points per component)
+__device__ __forceinline__ double postcov_prior(const PostcovParams& p, int R, int C, double diag_add) {
+  const int cr = R >= p.mp, cc = C >= p.mp;
+  const int i = R - cr * p.mp, j = C - cc * p.mp;
+  if (i >= p.m || j >= p.m) return R == C ? 1.0 : 0.0;
+  double ta, a1, a2, tb, b1, b2;
+  vec_point(p.vp, p.xg, i, ta, a1, a2);
+  vec_point(p.vp, p.xg, j, tb, b1, b2);
+  double k11, k12, k22;
+  vec_block_st(p.vp, ta - tb, a1 - b1, a2 - b2, k11, k12, k22);
+  const double k = (cr != cc) ? k12 : (cr ? k22 : k11);
+  return R == C ? k + diag_add : k;
+}
+
+__global__ __launch_bounds__(256, 2) void postcov_kernel(PostcovParams p) {
+  __shared__ double smem[2 * 2 * GBK * BS_NN];
+  constexpr int PANEL = GBK * BS_NN;
+
+  int bi, bj;
+  tri_tile(blockIdx.x, bi, bj);
+  const int i0 = bi * GBM, j0 = bj * GBN;
+  const bool diag_tile = bi == bj;   // one panel serves both operands
+  const double* __restrict__ V = p.V;
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wr = wid >> 1, wc = wid & 1;
+  const int lr = lane & 15, lk = lane >> 4;
+
+  d4 acc[4][4];
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = d4{0.0, 0.0, 0.0, 0.0};
+
+  // global -> register prefetch: 4 rows × 128 columns of each panel per pass
+  const int br = tid >> 6, bc = (tid & 63) * 2;
+  d2 ra[4], rb[4];
+  auto gload = [&](int k0) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      ra[s] = *reinterpret_cast<const d2*>(V + (int64_t)(k0 + br + 4 * s) * p.ldv + i0 + bc);
+    if (!diag_tile) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        rb[s] = *reinterpret_cast<const d2*>(V + (int64_t)(k0 + br + 4 * s) * p.ldv + j0 + bc);
+    }
+  };
+  auto swrite = [&](int buf) {
+    double* As = smem + buf * 2 * PANEL;
+    double* Bs = As + PANEL;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) *reinterpret_cast<d2*>(As + (br + 4 * s) * BS_NN + bc) = ra[s];
+    if (!diag_tile) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) *reinterpret_cast<d2*>(Bs + (br + 4 * s) * BS_NN + bc) = rb[s];
+    }
+  };
+
+  gload(0);
+  swrite(0);
+  __syncthreads();
+  int buf = 0;
+  for (int k0 = 0; k0 < p.n; k0 += GBK) {
+    const bool has_next = (k0 + GBK) < p.n;
+    if (has_next) gload(k0 + GBK);
+    const double* As = smem + buf * 2 * PANEL;
+    const double* Bs = diag_tile ? As : As + PANEL;
+#pragma unroll
+    for (int kk = 0; kk < GBK; kk += 4) {
+      double a[4], b[4];
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) a[mi] = As[(kk + lk) * BS_NN + wr * 64 + mi * 16 + lr];
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) b[ni] = Bs[(kk + lk) * BS_NN + wc * 64 + ni * 16 + lr];
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+    }
+    if (has_next) swrite(buf ^ 1);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  // acc[mi][ni][r] of lane (lr, lk) is element (R, C) = (rb0 + 16·mi + lk + 4r, cb0 + 16·ni + lr)
+  const int rb0 = i0 + wr * 64, cb0 = j0 + wc * 64;
+  double* __restrict__ Cm = p.C;
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      const int Cc = cb0 + ni * 16 + lr;
+      double v[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int R = rb0 + mi * 16 + lk + 4 * r;
+        v[r] = postcov_prior(p, R, Cc, p.diag_add) - acc[mi][ni][r];
+        if (!diag_tile || Cc <= R) Cm[(int64_t)R * p.ldc + Cc] = v[r];
+      }
+      // transpose the 4×4 (lk, r) block: afterwards v[r] is element (rb0 + 16·mi + 4·lk + r, Cc)
+      {
+        const bool o = lk & 1;
+        const double s0 = __shfl_xor(o ? v[0] : v[1], 16), s1 = __shfl_xor(o ? v[2] : v[3], 16);
+        if (o) { v[0] = s0; v[2] = s1; } else { v[1] = s0; v[3] = s1; }
+      }
+      {
+        const bool o = lk & 2;
+        const double s0 = __shfl_xor(o ? v[0] : v[2], 32), s1 = __shfl_xor(o ? v[1] : v[3], 32);
+        if (o) { v[0] = s0; v[1] = s1; } else { v[2] = s0; v[3] = s1; }
+      }
+      const int R0 = rb0 + mi * 16 + 4 * lk;
+      double* mrow = Cm + (int64_t)Cc * p.ldc + R0;   // the mirror: row Cc, columns R0..R0+3
+      if (!diag_tile) {
+        *reinterpret_cast<d4u*>(mrow) = d4u{v[0], v[1], v[2], v[3]};
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (Cc < R0 + r) mrow[r] = v[r];
+      }
+    }
+}
+
+inline int launch_postcov(const PostcovParams& p, hipStream_t s) {
+  if (p.q <= 0) return 0;
+  if ((p.q % GBM) || (p.n % GBK) || p.n <= 0 || p.q != 2 * p.mp) {
+    set_error("postcov: q must be 2·mp and a multiple of 128, n a positive multiple of 16");
+    return -2;
+  }
+  const int t = p.q / GBM;
+  postcov_kernel<<<dim3(t * (t + 1) / 2), 256, 0, s>>>(p);
+  return check_launch("postcov_kernel");
+}
+
+// Padded target count and matrix order of gp2d_predict_cov.
+constexpr int64_t postcov_mp(int64_t m) { return round_up(m < 1 ? 1 : m, PT_TILE); }
+constexpr int64_t postcov_q(int64_t m) { return 2 * postcov_mp(m); }
+
+// Workspace of gp2d_predict_cov: K*ᵀ (n × q) | V = W·K*ᵀ (n × q) | the mean's partial sums
+// ((n / MEAN_SEG) segments × q).
+struct PredictCovWork {
+  size_t Ks = 0, V = 0, pm = 0, total = 0;
+  constexpr PredictCovWork(int64_t n, int64_t m) {
+    const size_t nq = F64 * (size_t)(n > 0 ? n : 0) * (size_t)postcov_q(m);
+    V = nq;
+    pm = 2 * nq;
+    total = pm + F64 * (size_t)((n > 0 ? n : 0) / MEAN_SEG + 1) * (size_t)postcov_q(m);
+  }
+  struct Ptrs { double* Ks; double* V; double* pm; };
+  Ptrs at(void* w) const { return {work_at(w, Ks), work_at(w, V), work_at(w, pm)}; }
+};
+constexpr bool predict_cov_work_ok(int64_t n, int64_t m) {
+  const PredictCovWork w(n, m);
+  const size_t nq = F64 * (size_t)n * (size_t)postcov_q(m);
+  return regions_ok({w.Ks, w.V, w.pm, w.total}, {nq, nq, F64 * (size_t)(n / MEAN_SEG + 1) * (size_t)postcov_q(m)});
+}
+static_assert(predict_cov_work_ok(128, 1) && predict_cov_work_ok(384, 130) && predict_cov_work_ok(8192, 4096) &&
+                  postcov_q(1) == 128 && postcov_q(100) == 256 && postcov_q(130) == 384,
+              "predict_cov workspace: regions out of order, overlapping or misaligned");
+
+}  // namespace gp2d

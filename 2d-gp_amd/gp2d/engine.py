@@ -984,6 +984,144 @@ def predict_field(gp: GPFit, xg, field: str, compute_var: bool = True, chunk: in
     return mean, var
 
 
+def _predict_cov_padded(gp: GPFit, xg, diag_add: float):
+    """gp2d_predict_cov: (mean (2m,), the padded q × q covariance, m, mp) on the device."""
+    if not gp.kernel.is_vector or gp.kernel._KINDS[gp.kernel.kind] == N.KIND_SCALAR:
+        raise ValueError("the joint covariance needs a div-free, curl-free or mixed vector kernel "
+                         "(the scalar kind and the ARD family are not supported)")
+    if gp.W is None:
+        raise ValueError("predict_cov needs the fit's factor W = L⁻¹ (this fit keeps only its int8 planes)")
+    L = N.lib()
+    G = _as_points(xg, gp.kernel.input_dim, gp.device)
+    m = G.shape[0]
+    if m < 1:
+        raise ValueError("need at least one target point")
+    mp = padded_points(m)
+    q = 2 * mp
+    wbytes = int(L.gp2d_predict_cov_workspace(gp.n, m))
+    work = _workspace(wbytes, gp.device)
+    mean = torch.empty(2 * m, dtype=torch.float64, device=gp.device)
+    cov = torch.empty((q, q), dtype=torch.float64, device=gp.device)
+    desc = gp.kernel.desc()
+    N.check(L.gp2d_predict_cov(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
+                               _ptr(G), m, ctypes.byref(desc), float(diag_add), _ptr(mean), _ptr(cov), q,
+                               _ptr(work), wbytes, _stream_handle(gp.device)), "gp2d_predict_cov")
+    return mean, cov, m, mp
+
+
+def _valid_index(m: int, mp: int, device) -> torch.Tensor:
+    """Rows of the padded component-major layout that belong to the m points: [u(0..m), v(0..m)]."""
+    r = torch.arange(m, device=device)
+    return torch.cat([r, mp + r])
+
+
+def predict_cov(gp: GPFit, xg, diag_add: float = 0.0):
+    """Posterior mean and JOINT covariance of the velocity at the points xg: device tensors
+    (mean (2m,), cov (2m, 2m)), component-major [u(g_1..g_m), v(g_1..g_m)] like the mean.
+
+    cov = K(g, g) − K*·K_y⁻¹·K*ᵀ + diag_add·I, the matrix the reference forms before it takes the
+    diagonal (GP_laser.py:128-129), sklearn's predict(return_cov=True) and, with diag_add = noise,
+    GPy's predict(full_cov=True).  Its diagonal is predict's latent variance; the matrix is exactly
+    symmetric.  The mean is bit for bit gp2d_predict's.  Dense in the targets: 8·(2·⌈m/64⌉·64)²
+    bytes plus two n × q work matrices.
+
+    Works for fits of either variance engine (the product runs on the FP64 engine from the fit's
+    W; gp.x, gp.alpha and gp.W share one point order).  ValueError for the scalar kind, the ARD
+    family, and a fit without W."""
+    mean, cov, m, mp = _predict_cov_padded(gp, xg, diag_add)
+    if m == mp:
+        return mean, cov
+    idx = _valid_index(m, mp, gp.device)
+    return mean, cov.index_select(0, idx).index_select(1, idx)
+
+
+def _jitchol(A: torch.Tensor, maxtries: int, rows: torch.Tensor | None = None):
+    """jitchol's (L, jitter, retries taken).  rows: the rows whose diagonal entries set the
+    schedule's mean(diag) (all by default; sample_posterior leaves out the padding's ones)."""
+    n = A.shape[0]
+    if A.dim() != 2 or A.shape[1] != n or n % NB or n < NB or not A.is_cuda or A.dtype != torch.float64 \
+            or not A.is_contiguous():
+        raise ValueError("jitchol: A must be a contiguous float64 device matrix of order a multiple of 128")
+    dev = A.device
+    _require_device(dev)
+    L = N.lib()
+    A0 = A.clone()   # gp2d_potrf overwrites A, failed or not
+    dinv = torch.empty((n // NB, NB, NB), dtype=torch.float64, device=dev)
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+
+    def factor() -> bool:
+        N.check(L.gp2d_potrf(_ptr(A), n, n, _ptr(dinv), _ptr(info), None, 0, _stream_handle(dev)), "gp2d_potrf")
+        return int(info.item()) == 0
+
+    if factor():
+        return A, 0.0, 0
+    d0 = A0.diagonal()
+    diag = float(np.mean((d0 if rows is None else d0.index_select(0, rows)).cpu().numpy()))
+    if not (np.isfinite(diag) and diag > 0.0):
+        raise np.linalg.LinAlgError("not pd: non-positive diagonal elements")
+    jit = diag * 1e-6
+    for t in range(1, int(maxtries) + 1):
+        if not np.isfinite(jit):
+            break
+        A.copy_(A0)
+        A.diagonal().add_(jit)
+        if factor():
+            return A, jit, t
+        jit *= 10.0
+    raise np.linalg.LinAlgError("not positive definite, even with jitter.")
+
+
+def jitchol(A: torch.Tensor, maxtries: int = 5):
+    """Cholesky factor of a device SPD matrix with GPy's jitchol retry: (L, jitter).
+
+    A (order a multiple of 128, contiguous float64) is factored IN PLACE by gp2d_potrf: on return
+    it holds L (lower, zeros above) with L·Lᵀ = A + jitter·I.  jitter is 0.0 when the plain
+    factorisation succeeds; otherwise the schedule fit(jitchol=k) documents — mean(diag A)·1e-6,
+    ten times larger on each further try, up to maxtries tries — and numpy.linalg.LinAlgError after
+    the last (A then holds the last failed try).  A failed factorisation is a status word, never a
+    device fault.  Costs one copy of A, kept for the retries."""
+    L, jit, _ = _jitchol(A, maxtries)
+    return L, jit
+
+
+def sample_posterior(gp: GPFit, xg, n_samples: int, seed: int = 0, z: torch.Tensor | None = None,
+                     jitter: float = 0.0, maxtries: int = 5):
+    """Conditional simulations: n_samples joint draws of the velocity at the points xg from the
+    posterior N(mean, Σ) — sklearn's sample_y, GPy's posterior_samples_f.  Returns (samples
+    (S, 2m) on the device, each row [u(g_1..g_m), v(g_1..g_m)], info).
+
+    samples = mean + (L·z)ᵀ with L·Lᵀ = Σ + (jitter + retry jitter)·I, Σ the latent covariance of
+    predict_cov on its padded layout, factored by jitchol: the Σ of a dense grid is numerically
+    singular (smallest eigenvalue at rounding level, either sign), so the retry is part of the
+    contract (its mean(diag) is taken over Σ's own diagonal, without the padding's ones).  info =
+    {'jitter': the total added to the diagonal, 'tries': retries taken (0: the first factorisation
+    succeeded)}.  z: (2m, S) standard normals in the component order; by default
+    torch.randn on the device from a torch.Generator seeded with `seed` (the same seed gives the
+    same samples).  L·z runs on the FP64 GEMM core (gemm)."""
+    mean, cov, m, mp = _predict_cov_padded(gp, xg, 0.0)
+    dev = gp.device
+    S = int(n_samples)
+    if z is None:
+        if S < 1:
+            raise ValueError("n_samples must be at least 1")
+        g = torch.Generator(device=dev)
+        g.manual_seed(int(seed))
+        z = torch.randn((2 * m, S), generator=g, device=dev, dtype=torch.float64)
+    else:
+        z = _as_matrix(z, dev)
+        if tuple(z.shape) != (2 * m, S):
+            raise ValueError(f"z must have shape (2m, n_samples) = ({2 * m}, {S}); got {tuple(z.shape)}")
+    if jitter:
+        cov.diagonal().add_(float(jitter))
+    # padded points are identity rows and columns, decoupled from the rest: the valid rows and
+    # columns of L are the factor of the valid part of Σ, and the schedule's mean(diag) is Σ's
+    idx = _valid_index(m, mp, dev)
+    L, jit, tries = _jitchol(cov, maxtries, rows=idx)
+    Lv = L if m == mp else L.index_select(0, idx).index_select(1, idx)
+    samples = gemm(Lv, z, device=dev).t() + mean[None, :]
+    return samples.contiguous(), {"jitter": float(jitter) + jit, "tries": tries}
+
+
 def note_guard(stats: dict | None, gp: GPFit):
     """Record a checked fit's accuracy-guard decision in a job stream's `stats` (stats['guard'],
     one dict per job in job order: engine, wbits, kbits, vmin_over_kss, wmax, est)."""

@@ -182,6 +182,33 @@ class Krig:
         shp = [np.size(y), -1]
         return {name: (mu.reshape(shp), var.reshape(shp)) for name, (mu, var) in self.predict_fields(pts).items()}
 
+    # ------------------------------------------------------------------ joint covariance, samples
+    def predict_cov(self, Xg):
+        """(mean (2M, 1), cov (2M, 2M)) numpy arrays: the posterior mean and the full latent
+        covariance Kss − Ks·Ki·Ksᵀ of GP_laser.py:128-129 (of which predict returns the diagonal),
+        as sklearn's predict(return_cov=True) and GPy's predict(full_cov=True) minus its noise;
+        rows and columns [u(M), v(M)] (engine.predict_cov)."""
+        self._check()
+        mu, cov = E.predict_cov(self.gp, Xg)
+        return _to_numpy(mu)[:, None], _to_numpy(cov)
+
+    def sample(self, Xg, n_samples: int, seed: int = 0):
+        """n_samples joint draws of the velocity at the points Xg from the posterior: (S, 2M) numpy,
+        each row [u(M), v(M)] — sklearn's sample_y / GPy's posterior_samples_f
+        (engine.sample_posterior; the same seed gives the same draws)."""
+        self._check()
+        return _to_numpy(E.sample_posterior(self.gp, Xg, n_samples, seed=seed)[0])
+
+    def sample_grid(self, x, y, n_samples: int, seed: int = 0):
+        """sample on the grid meshgrid(x, y) of predict_grid: (us, vs), each (S, y.size, x.size),
+        us[s] and vs[s] one simulated velocity field laid out as predict_grid's uf and vf."""
+        X, Y = np.meshgrid(x, y)
+        pts = np.stack([X.reshape(-1), Y.reshape(-1)], 1)
+        s = self.sample(pts, n_samples, seed=seed)
+        M = pts.shape[0]
+        shp = [s.shape[0], np.size(y), -1]
+        return s[:, :M].reshape(shp), s[:, M:].reshape(shp)
+
     # ------------------------------------------------------------------ hyperparameters
     def log_likelihood(self, eval_gradient: bool = False):
         """GPy model.log_likelihood() / sklearn log_marginal_likelihood() of the current fit;

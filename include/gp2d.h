@@ -212,6 +212,31 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
                        int compute_var, double* mean, double* var, int64_t chunk,
                        void* work, size_t work_bytes, void* stream);
 
+/* ---- predict: joint posterior covariance of the velocity at the target points -------
+ * The reference forms the full matrix
+ *   Kss = compute_K(Xs, Ys, …);  Cov = Kss − np.dot(Ks, np.dot(Ki, Ks.T))   (GP_laser.py:128-129)
+ * and keeps its diagonal (:130-131); sklearn predict(return_cov=True) / sample_y and GPy
+ * predict(full_cov=True) / posterior_samples_f return or draw from the same matrix.
+ * gp2d_predict_cov: mean (2m doubles, [u…, v…]; bit for bit gp2d_predict's mean) and
+ *   cov = K(g, g) − VᵀV + diag_add·I,  V = W·K*ᵀ,
+ * a q × q matrix with leading dimension ldc ≥ q, q = 2·mp, mp = ⌈m/64⌉·64, rows and columns
+ * component-major [u(g_1..g_m), pad, v(g_1..g_m), pad] as K_y is laid out.  Rows and columns of
+ * padded points are identity, and cov is exactly symmetric (each pair (i, j), (j, i) is stored
+ * from one register value), so the buffer can go straight into gp2d_potrf.  diag_add: 0 for the
+ * latent covariance (the reference's Cov), the noise for GPy's full_cov convention.
+ * VᵀV runs on the FP64 MFMA cores over lower 128×128 tiles with the prior block regenerated in
+ * the epilogue (csrc/postcov.hpp): no q × q prior is stored; no atomics, fixed summation order.
+ * Kernels: VECTOR2D and VECTOR_ST of kind DIVFREE, CURLFREE or MIXED; KIND_SCALAR and the ARD
+ * family are refused, as in gp2d_predict_field.  W, alpha, xtr, ntr, ntr_pad as for gp2d_predict
+ * (n = 2·ntr_pad).  Workspace: gp2d_predict_cov_workspace(n, m) bytes (K*ᵀ and V, n × q each,
+ * and the mean's partial sums).                                                            */
+size_t gp2d_predict_cov_workspace(int64_t n, int64_t m);
+int gp2d_predict_cov(const double* W, int64_t n, int64_t ldw, const double* alpha,
+                     const double* xtr, int64_t ntr, int64_t ntr_pad,
+                     const double* xg, int64_t m, const gp2d_kernel_t* k, double diag_add,
+                     double* mean, double* cov, int64_t ldc,
+                     void* work, size_t work_bytes, void* stream);
+
 /* ---- predict, FP64-accurate variance on the INT8 matrix cores (Ozaki scheme II) -----
  * Same results contract as gp2d_predict (1e-10 relative parity gate) for the vector2d
  * family; the variance contraction ‖W k*‖² runs as nmod exact int8 GEMMs
@@ -486,7 +511,8 @@ int gp2d_status_flip(int* status, int count, void* stream);
 
 /* ---- instrumentation ------------------------------------------------------------
  * When enabled, every launch of the predict variance kernel (the dominant
- * kernel) is bracketed by hipEvents on its stream; gp2d_timing_read()
+ * kernel) and of gp2d_predict_cov's VᵀV kernel (2N·(2m)² flop, its lower half)
+ * is bracketed by hipEvents on its stream; gp2d_timing_read()
  * synchronises those events and returns the summed milliseconds, the launch
  * count and the summed algorithmic flop count, then resets the counters.        */
 void gp2d_timing_enable(int on);
