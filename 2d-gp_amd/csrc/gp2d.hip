@@ -13,6 +13,7 @@
 #include "predict.hpp"
 #include "fields.hpp"
 #include "postcov.hpp"
+#include "predict_host.hpp"
 #include "ozaki.hpp"
 #include "ozaki_host.hpp"
 #include "factor_host.hpp"
@@ -28,6 +29,7 @@
 #include <cstring>
 #include <cmath>
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -53,6 +55,32 @@ struct Timing {
   }
 };
 static Timing g_timing;
+
+// Times what is enqueued on the stream from its construction to stop() or the end of its scope,
+// when the hooks are on (and `enabled`): an event pair from the pool around that span, recorded with
+// its flop count — also when a launch inside failed and the function returned, so the pair goes
+// back to the pool at the next gp2d_timing_read().
+struct TimedLaunch {
+  TimedLaunch(hipStream_t stream, double flop, bool enabled = true) : s(stream), flops(flop) {
+    std::lock_guard<std::mutex> lk(g_timing.mu);
+    if (enabled && g_timing.on) { e0 = g_timing.get(); e1 = g_timing.get(); hipEventRecord(e0, s); }
+  }
+  void stop() {
+    if (!e0) return;
+    std::lock_guard<std::mutex> lk(g_timing.mu);
+    hipEventRecord(e1, s);
+    g_timing.ev.push_back({e0, e1});
+    g_timing.flops.push_back(flops);
+    e0 = nullptr;
+  }
+  ~TimedLaunch() { stop(); }
+  TimedLaunch(const TimedLaunch&) = delete;
+  TimedLaunch& operator=(const TimedLaunch&) = delete;
+ private:
+  hipStream_t s;
+  double flops;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+};
 
 static bool is_vector_family(const gp2d_kernel_t* k) {
   return k->family == GP2D_FAMILY_VECTOR2D || k->family == GP2D_FAMILY_VECTOR_ST;
@@ -974,11 +1002,86 @@ int gp2d_potrs_inv(const double* W, int64_t n, int64_t ldw, const double* y, dou
 }
 
 // ---------------------------------------------------------------------- PREDICT
+// The launches every predict entry is built from (workspace layouts: predict_host.hpp).
+static int launch_mean_partials(const double* B, int64_t ncols, int64_t n, const double* alpha, double* pm,
+                                hipStream_t s) {
+  const dim3 grid((unsigned)((ncols + 255) / 256), (unsigned)predict_segments(n));
+  mean_part_kernel<<<grid, 256, 0, s>>>(B, ncols, ncols, alpha, pm);
+  return check_launch("mean_part_kernel");
+}
+
+// predict_finalize_kernel's arguments: the partial sums and their segment counts, the chunk (ncols
+// columns = components of cp padded, cv valid targets, the first being target c0 of m), the
+// variance's terms (prior − Σ v² + add, clipped at 0 if asked), the outputs and the caller's order
+struct Finalize {
+  const double* pm; int64_t nmseg;
+  const double* P; int64_t npseg;
+  int64_t ncols, cp, cv, c0, m;
+  double prior, add;
+  int clip, compute_var;
+  double* mean; double* var;
+  const int64_t* order;
+};
+static int launch_finalize(const Finalize& f, hipStream_t s) {
+  predict_finalize_kernel<<<(unsigned)((f.ncols + 63) / 64), 64, 0, s>>>(
+      f.pm, f.nmseg, f.P, f.npseg, f.ncols, f.cp, f.cv, f.c0, f.m, f.prior, f.add, f.clip, f.compute_var, f.mean,
+      f.var, f.order);
+  return check_launch("predict_finalize_kernel");
+}
+
+// V = W·K*ᵀ: W = L⁻¹ (n × n, lower triangular), K*ᵀ = B (n × ncols).  The caller adds P / ldp
+// (EPI_COLSQ: Σ v² per column) or C / ldc (EPI_STORE: V itself).
+static GemmParams wk_gemm_params(const double* W, int64_t ldw, int64_t n, const double* B, int64_t ncols) {
+  GemmParams p = gemm_params();
+  p.A = W; p.lda = ldw;
+  p.B = B; p.ldb = ncols;
+  p.M = (int)n; p.N = (int)ncols; p.K = (int)n;
+  p.a_lower = 1; p.rev_rows = 1;
+  p.xcd_cols = 0;  // XCD-grouped order measured 4% slower (64.9 vs 67.6 TF/s); kept for study
+  return p;
+}
+
+// What differs between the chunked predicts: components per target, the variance's terms, whether
+// the product goes to the timing hooks, and the chunk's cross-covariance — assemble(the chunk's
+// targets, valid count, padded count, out) writes K*ᵀ (n × bd·cp: rows = training components,
+// columns = target components).
+struct ChunkedPredict {
+  int bd;
+  double prior, add = 0.0;
+  int clip = 0;
+  bool timed = false;
+  std::function<int(const double* xg, int64_t cv, int64_t cp, double* Ks)> assemble;
+};
+
+// One chunked predict over the m targets (dim coordinates each): per chunk assemble, mean partials,
+// Σ v² partials of W·K*ᵀ if the variance is asked for, finalize.
+static int predict_chunks(const ChunkedPredict& v, const double* W, int64_t n, int64_t ldw, const double* alpha,
+                          int64_t ntr, const double* xg, int dim, int64_t m, int compute_var, double* mean,
+                          double* var, int64_t chunk, void* work, hipStream_t s) {
+  static_assert(GBN == 2 * PT_TILE, "a chunk's bd·cp columns fill whole GEMM column tiles");
+  const auto [Ks, pm, P] = PredictWork(n, v.bd * chunk).at(work);
+  const int64_t nseg = predict_segments(n);
+  for (int64_t c0 = 0; c0 < m; c0 += chunk) {
+    const int64_t cv = std::min<int64_t>(chunk, m - c0);
+    const int64_t cp = round_up(cv, GBN / v.bd);
+    const int64_t ncols = v.bd * cp;
+    GP2D_CHECK(v.assemble(xg + c0 * dim, cv, cp, Ks));
+    GP2D_CHECK(launch_mean_partials(Ks, ncols, n, alpha, pm, s));
+    if (compute_var) {
+      GemmParams p = wk_gemm_params(W, ldw, n, Ks, ncols);
+      p.P = P; p.ldp = ncols;
+      const double nv = (double)v.bd * (double)ntr;  // algorithmic order (valid points)
+      TimedLaunch t(s, (double)v.bd * (double)cv * nv * nv, v.timed);  // 2·(2N)² per point (vector2d)
+      GP2D_CHECK((launch_gemm<false, EPI_COLSQ>(p, 1, s)));
+    }
+    GP2D_CHECK(launch_finalize({pm, nseg, P, nseg, ncols, cp, cv, c0, m, v.prior, v.add, v.clip, compute_var, mean,
+                                var, nullptr}, s));
+  }
+  return 0;
+}
+
 size_t gp2d_predict_workspace(int64_t n, int64_t chunk, int bd) {
-  const int64_t cp = round_up(chunk < 1 ? 1 : chunk, PT_TILE);
-  const int64_t ncols = bd * cp;
-  const int64_t ncols_t = round_up(ncols, GBN);
-  return sizeof(double) * ((size_t)n * ncols_t + 2 * (size_t)(n / MEAN_SEG + 1) * ncols_t);
+  return PredictWork(n, predict_sized_cols(chunk, bd)).total;
 }
 
 int gp2d_predict(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
@@ -995,52 +1098,16 @@ int gp2d_predict(const double* W, int64_t n, int64_t ldw, const double* alpha, c
   GP2D_REQUIRE(var_mode >= 0 && var_mode <= 2, "predict: bad var_mode");
   if (m <= 0) return 0;
   hipStream_t s = S(stream);
-  const int64_t ncols_max = bd * chunk;
-  double* Bm = reinterpret_cast<double*>(work);
-  double* pm = Bm + (size_t)n * ncols_max;
-  double* P = pm + (size_t)(n / MEAN_SEG + 1) * ncols_max;
-  const double kss = gp2d_kernel_diag(k);
-  const double add = (var_mode == GP2D_VAR_LATENT) ? 0.0 : noise;
-  const int clip = (var_mode == GP2D_VAR_CLIPPED);
-  const int dim = point_dim(k);
-
-  for (int64_t c0 = 0; c0 < m; c0 += chunk) {
-    const int64_t cv = std::min<int64_t>(chunk, m - c0);
-    const int64_t cp = round_up(cv, (bd == 2) ? PT_TILE : GBN);
-    const int64_t ncols = bd * cp;
-    // K*ᵀ chunk: rows = training components, cols = grid components
-    GP2D_CHECK(assemble_impl(xtr, ntr, ntr_pad, xg + c0 * dim, cv, cp, k, 0.0, 0, Bm, ncols, s));
-    const int64_t nmseg = n / MEAN_SEG;
-    mean_part_kernel<<<dim3((unsigned)((ncols + 255) / 256), (unsigned)nmseg), 256, 0, s>>>(Bm, ncols, ncols, alpha, pm);
-    GP2D_CHECK(check_launch("mean_part_kernel"));
-    const int64_t npseg = n / GBM;
-    if (compute_var) {
-      GemmParams p = gemm_params();
-      p.A = W; p.lda = ldw;
-      p.B = Bm; p.ldb = ncols;
-      p.M = (int)n; p.N = (int)ncols; p.K = (int)n;
-      p.a_lower = 1; p.rev_rows = 1;
-      p.xcd_cols = 0;  // XCD-grouped order measured 4% slower (64.9 vs 67.6 TF/s); kept for study
-      p.P = P; p.ldp = ncols;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      {
-        std::lock_guard<std::mutex> lk(g_timing.mu);
-        if (g_timing.on) { e0 = g_timing.get(); e1 = g_timing.get(); hipEventRecord(e0, s); }
-      }
-      GP2D_CHECK((launch_gemm<false, EPI_COLSQ>(p, 1, s)));
-      if (e0) {
-        std::lock_guard<std::mutex> lk(g_timing.mu);
-        hipEventRecord(e1, s);
-        g_timing.ev.push_back({e0, e1});
-        const double nv = (double)bd * (double)ntr;  // algorithmic order (valid points)
-        g_timing.flops.push_back((double)bd * (double)cv * nv * nv);  // 2·(2N)² per point (vector2d)
-      }
-    }
-    predict_finalize_kernel<<<(unsigned)((ncols + 63) / 64), 64, 0, s>>>(
-        pm, nmseg, P, npseg, ncols, cp, cv, c0, m, kss, add, clip, compute_var, mean, var, nullptr);
-    GP2D_CHECK(check_launch("predict_finalize_kernel"));
-  }
-  return 0;
+  ChunkedPredict v;
+  v.bd = bd;
+  v.prior = gp2d_kernel_diag(k);
+  v.add = (var_mode == GP2D_VAR_LATENT) ? 0.0 : noise;
+  v.clip = (var_mode == GP2D_VAR_CLIPPED);
+  v.timed = true;
+  v.assemble = [=](const double* xc, int64_t cv, int64_t cp, double* Ks) {
+    return assemble_impl(xtr, ntr, ntr_pad, xc, cv, cp, k, 0.0, 0, Ks, bd * cp, s);
+  };
+  return predict_chunks(v, W, n, ldw, alpha, ntr, xg, point_dim(k), m, compute_var, mean, var, chunk, work, s);
 }
 
 // ------------------------------------------------------- PREDICT (derived fields)
@@ -1087,38 +1154,18 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
     }
     return 0;
   }
-  double* Bm = reinterpret_cast<double*>(work);
-  double* pm = Bm + (size_t)n * chunk;
-  double* P = pm + (size_t)(n / MEAN_SEG + 1) * chunk;
-  const double prior = gp2d_field_prior_var(k, field);
   const FieldParams fp = make_field_params(k, field);
-  const int dim = point_dim(k);
-  const int64_t nmseg = n / MEAN_SEG, npseg = n / GBM;
-
-  for (int64_t c0 = 0; c0 < m; c0 += chunk) {
-    const int64_t cv = std::min<int64_t>(chunk, m - c0);
-    const int64_t cp = round_up(cv, GBN);
+  // one component per target: the prior is the field's prior variance, no noise, no clipping; untimed
+  ChunkedPredict v;
+  v.bd = 1;
+  v.prior = gp2d_field_prior_var(k, field);
+  v.assemble = [=](const double* xc, int64_t cv, int64_t cp, double* Ks) {
     // cov(observations, field) for the chunk: rows = training components, cols = target points
-    assemble_field_kernel<<<dim3((unsigned)(cp / 64), (unsigned)((ntr_pad + ASM_ROWS - 1) / ASM_ROWS)), 256, 0, s>>>(
-        xtr, ntr, ntr_pad, xg + c0 * dim, cv, cp, fp, Bm);
-    GP2D_CHECK(check_launch("assemble_field_kernel"));
-    mean_part_kernel<<<dim3((unsigned)((cp + 255) / 256), (unsigned)nmseg), 256, 0, s>>>(Bm, cp, cp, alpha, pm);
-    GP2D_CHECK(check_launch("mean_part_kernel"));
-    if (compute_var) {
-      GemmParams p = gemm_params();
-      p.A = W; p.lda = ldw;
-      p.B = Bm; p.ldb = cp;
-      p.M = (int)n; p.N = (int)cp; p.K = (int)n;
-      p.a_lower = 1; p.rev_rows = 1;
-      p.P = P; p.ldp = cp;
-      GP2D_CHECK((launch_gemm<false, EPI_COLSQ>(p, 1, s)));
-    }
-    // one component of cp columns: kss = the field's prior variance, no noise, no clipping
-    predict_finalize_kernel<<<(unsigned)((cp + 63) / 64), 64, 0, s>>>(pm, nmseg, P, npseg, cp, cp, cv, c0, m, prior, 0.0,
-                                                                     0, compute_var, mean, var, nullptr);
-    GP2D_CHECK(check_launch("predict_finalize_kernel"));
-  }
-  return 0;
+    const dim3 grid((unsigned)(cp / 64), (unsigned)((ntr_pad + ASM_ROWS - 1) / ASM_ROWS));
+    assemble_field_kernel<<<grid, 256, 0, s>>>(xtr, ntr, ntr_pad, xc, cv, cp, fp, Ks);
+    return check_launch("assemble_field_kernel");
+  };
+  return predict_chunks(v, W, n, ldw, alpha, ntr, xg, point_dim(k), m, compute_var, mean, var, chunk, work, s);
 }
 
 // ------------------------------------------------- PREDICT (joint posterior covariance)
@@ -1144,20 +1191,13 @@ int gp2d_predict_cov(const double* W, int64_t n, int64_t ldw, const double* alph
 
   // K*ᵀ: rows = training components, columns = target components; the mean as in gp2d_predict
   GP2D_CHECK(assemble_impl(xtr, ntr, ntr_pad, xg, m, mp, k, 0.0, 0, w.Ks, q, s));
-  const int64_t nmseg = n / MEAN_SEG;
-  mean_part_kernel<<<dim3((unsigned)((q + 255) / 256), (unsigned)nmseg), 256, 0, s>>>(w.Ks, q, q, alpha, w.pm);
-  GP2D_CHECK(check_launch("mean_part_kernel"));
-  predict_finalize_kernel<<<(unsigned)((q + 63) / 64), 64, 0, s>>>(w.pm, nmseg, nullptr, 0, q, mp, m, 0, m, 0.0, 0.0, 0,
-                                                                   0, mean, nullptr, nullptr);
-  GP2D_CHECK(check_launch("predict_finalize_kernel"));
+  GP2D_CHECK(launch_mean_partials(w.Ks, q, n, alpha, w.pm, s));
+  GP2D_CHECK(launch_finalize({w.pm, predict_segments(n), nullptr, 0, q, mp, m, 0, m, 0.0, 0.0, 0, 0, mean, nullptr,
+                              nullptr}, s));
 
   // V = W·K*ᵀ, gp2d_predict's product stored
-  GemmParams g = gemm_params();
-  g.A = W; g.lda = ldw;
-  g.B = w.Ks; g.ldb = q;
+  GemmParams g = wk_gemm_params(W, ldw, n, w.Ks, q);
   g.C = w.V; g.ldc = q;
-  g.M = (int)n; g.N = (int)q; g.K = (int)n;
-  g.a_lower = 1; g.rev_rows = 1;
   GP2D_CHECK((launch_gemm<false, EPI_STORE>(g, 1, s)));
 
   // Σ = K(g, g) − VᵀV (+ diag_add·I), padded points identity
@@ -1169,19 +1209,8 @@ int gp2d_predict_cov(const double* W, int64_t n, int64_t ldw, const double* alph
   p.vp = make_vec_params(k);
   p.diag_add = diag_add;
   p.C = cov; p.ldc = ldc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(g_timing.mu);
-    if (g_timing.on) { e0 = g_timing.get(); e1 = g_timing.get(); hipEventRecord(e0, s); }
-  }
-  GP2D_CHECK(launch_postcov(p, s));
-  if (e0) {
-    std::lock_guard<std::mutex> lk(g_timing.mu);
-    hipEventRecord(e1, s);
-    g_timing.ev.push_back({e0, e1});
-    g_timing.flops.push_back(2.0 * (double)ntr * (double)(2 * m) * (double)(2 * m));  // 2N·(2m)², the lower half
-  }
-  return 0;
+  TimedLaunch t(s, 2.0 * (double)ntr * (double)(2 * m) * (double)(2 * m));  // 2N·(2m)², the lower half
+  return launch_postcov(p, s);
 }
 
 // ------------------------------------------------------------ PREDICT (Ozaki-II)
@@ -1442,11 +1471,8 @@ static int predict_ozaki_impl(const int8_t* wres, const double* rowscale, int nm
       GP2D_CHECK(check_launch("ozaki_slab_list_kernel"));
     }
     if (compute_var) {
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      {
-        std::lock_guard<std::mutex> lk(g_timing.mu);
-        if (g_timing.on) { e0 = g_timing.get(); e1 = g_timing.get(); hipEventRecord(e0, s); }
-      }
+      const double nv = 2.0 * (double)ntr;
+      TimedLaunch timed(s, 2.0 * (double)cv * nv * nv);  // FP64-equivalent algorithmic flop
       // small n: every modulus in one launch (moduli on grid.z: no launch gap and no tail
       // between the moduli, −3 % per chunk at n = 2048, profiles/r04_zbatch.txt); large n:
       // one launch per modulus (the same within 0.2 %)
@@ -1468,20 +1494,13 @@ static int predict_ozaki_impl(const int8_t* wres, const double* rowscale, int nm
                                                                 zb);
         GP2D_CHECK(check_launch("igemm_nt_mod_kernel"));
       }
-      if (e0) {
-        std::lock_guard<std::mutex> lk(g_timing.mu);
-        hipEventRecord(e1, s);
-        g_timing.ev.push_back({e0, e1});
-        const double nv = 2.0 * (double)ntr;
-        g_timing.flops.push_back(2.0 * (double)cv * nv * nv);  // FP64-equivalent algorithmic flop
-      }
+      timed.stop();
       const dim3 cgrid((unsigned)((ncols + OZ_CRT_BCOLS - 1) / OZ_CRT_BCOLS), (unsigned)npseg);
       ozaki_crt_colsq_kernel<<<cgrid, 256, 0, s>>>(cres, n, ncols, oc, rowscale, P);
       GP2D_CHECK(check_launch("ozaki_crt_colsq_kernel"));
     }
-    predict_finalize_kernel<<<(unsigned)((ncols + 63) / 64), 64, 0, s>>>(
-        pm, nmseg, P, npseg, ncols, cp, cv, c0, m, kss, add, clip, compute_var, mean, var, out_order);
-    GP2D_CHECK(check_launch("predict_finalize_kernel"));
+    GP2D_CHECK(launch_finalize({pm, nmseg, P, npseg, ncols, cp, cv, c0, m, kss, add, clip, compute_var, mean, var,
+                                out_order}, s));
   }
   return 0;
 }

@@ -8,7 +8,7 @@
 // (of which it keeps the diagonal, :130-131), sklearn predict(return_cov=True) and GPy
 // predict(full_cov=True).  V is gp2d_predict's own product stored instead of column-squared
 // (gemm_f64_kernel<false, EPI_STORE>, a_lower); this header holds the TN product VᵀV with the prior
-// regenerated in its epilogue, and the workspace layout of gp2d_predict_cov.
+// regenerated in its epilogue (the workspace layout of gp2d_predict_cov is in predict_host.hpp).
 //
 // postcov_kernel: one lower 128×128 tile of Σ per 256-thread workgroup (tri_tile, as the c_lower
 // SYRK), 4 waves as 2×2, each wave 4×4 MFMA tiles of v_mfma_f64_16x16x4_f64.  Both operands are
@@ -181,31 +181,5 @@ inline int launch_postcov(const PostcovParams& p, hipStream_t s) {
   postcov_kernel<<<dim3(t * (t + 1) / 2), 256, 0, s>>>(p);
   return check_launch("postcov_kernel");
 }
-
-// Padded target count and matrix order of gp2d_predict_cov.
-constexpr int64_t postcov_mp(int64_t m) { return round_up(m < 1 ? 1 : m, PT_TILE); }
-constexpr int64_t postcov_q(int64_t m) { return 2 * postcov_mp(m); }
-
-// Workspace of gp2d_predict_cov: K*ᵀ (n × q) | V = W·K*ᵀ (n × q) | the mean's partial sums
-// ((n / MEAN_SEG) segments × q).
-struct PredictCovWork {
-  size_t Ks = 0, V = 0, pm = 0, total = 0;
-  constexpr PredictCovWork(int64_t n, int64_t m) {
-    const size_t nq = F64 * (size_t)(n > 0 ? n : 0) * (size_t)postcov_q(m);
-    V = nq;
-    pm = 2 * nq;
-    total = pm + F64 * (size_t)((n > 0 ? n : 0) / MEAN_SEG + 1) * (size_t)postcov_q(m);
-  }
-  struct Ptrs { double* Ks; double* V; double* pm; };
-  Ptrs at(void* w) const { return {work_at(w, Ks), work_at(w, V), work_at(w, pm)}; }
-};
-constexpr bool predict_cov_work_ok(int64_t n, int64_t m) {
-  const PredictCovWork w(n, m);
-  const size_t nq = F64 * (size_t)n * (size_t)postcov_q(m);
-  return regions_ok({w.Ks, w.V, w.pm, w.total}, {nq, nq, F64 * (size_t)(n / MEAN_SEG + 1) * (size_t)postcov_q(m)});
-}
-static_assert(predict_cov_work_ok(128, 1) && predict_cov_work_ok(384, 130) && predict_cov_work_ok(8192, 4096) &&
-                  postcov_q(1) == 128 && postcov_q(100) == 256 && postcov_q(130) == 384,
-              "predict_cov workspace: regions out of order, overlapping or misaligned");
 
 }  // namespace gp2d

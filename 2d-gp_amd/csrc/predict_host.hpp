@@ -1,0 +1,81 @@
+// predict_host.hpp — the two workspace layouts of the FP64 predicts (gp2d_predict and
+// gp2d_predict_field; gp2d_predict_cov), as byte-offset tables.  gp2d.hip takes every FP64 predict
+// workspace size it reports and every pointer it carves from here; nothing else knows the layouts
+// (the kernels in predict.hpp, gemm_f64.hpp and postcov.hpp get plain pointers).
+#pragma once
+#include "factor_host.hpp"
+#include "gemm_f64.hpp"
+#include "predict.hpp"
+
+namespace gp2d {
+
+// Partial sums of a reduction over the n rows: one row of ncols per 128-row segment — the mean's
+// (mean_part_kernel's grid.y, MEAN_SEG rows each) and the variance's Σ v² (the EPI_COLSQ epilogue,
+// GBM rows each: the same count) — sized for one row more.
+static_assert(MEAN_SEG == GBM, "the mean's and the COLSQ partials share one segment count");
+constexpr int64_t predict_segments(int64_t n) { return n / MEAN_SEG; }
+constexpr size_t predict_partial_bytes(int64_t n, int64_t ncols) {
+  return F64 * (size_t)(predict_segments(n) + 1) * (size_t)ncols;
+}
+
+// Columns a chunked predict's workspace is sized for: bd components of `chunk` targets padded to
+// whole point tiles, rounded up to whole GEMM column tiles.  chunk < 1 sizes as one tile.
+constexpr int64_t predict_sized_cols(int64_t chunk, int bd) {
+  return round_up(bd * round_up(chunk < 1 ? 1 : chunk, PT_TILE), GBN);
+}
+
+// Workspace of gp2d_predict and gp2d_predict_field: K*ᵀ of a chunk (n × ncols) | the mean's
+// partial sums | the Σ v² partial sums.  The exported sizes are PredictWork(n, predict_sized_cols(
+// chunk, bd)); the entries carve with ncols = bd·chunk (gp2d_predict) and ncols = chunk
+// (gp2d_predict_field), which their argument checks (chunk a positive multiple of 64, the column
+// count a multiple of 128) make equal to the sized count — a workspace of the exported size is
+// exactly what a call uses.  (n < 1 is no call's shape; the size functions answer it with this same
+// arithmetic, n = 0: the two partial rows.)
+struct PredictWork {
+  size_t Ks = 0, pm = 0, P = 0, total = 0;
+  constexpr PredictWork(int64_t n, int64_t ncols) {
+    pm = F64 * (size_t)n * (size_t)ncols;
+    P = pm + predict_partial_bytes(n, ncols);
+    total = P + predict_partial_bytes(n, ncols);
+  }
+  struct Ptrs { double* Ks; double* pm; double* P; };
+  Ptrs at(void* w) const { return {work_at(w, Ks), work_at(w, pm), work_at(w, P)}; }
+};
+constexpr bool predict_work_ok(int64_t n, int64_t ncols) {
+  const PredictWork w(n, ncols);
+  const size_t part = F64 * (size_t)(n / 128 + 1) * (size_t)ncols;
+  return regions_ok({w.Ks, w.pm, w.P, w.total}, {F64 * (size_t)n * (size_t)ncols, part, part}) &&
+         w.total == F64 * (size_t)ncols * (size_t)(n + 2 * (n / 128 + 1));
+}
+static_assert(predict_work_ok(128, 128) && predict_work_ok(256, 256) && predict_work_ok(8192, 16384) &&
+                  predict_sized_cols(8192, 2) == 16384 && predict_sized_cols(64, 1) == 128 &&
+                  predict_sized_cols(0, 2) == 128 && predict_sized_cols(100, 2) == 256,
+              "predict workspace: regions out of order, overlapping or misaligned");
+
+// Padded target count and matrix order of gp2d_predict_cov.
+constexpr int64_t postcov_mp(int64_t m) { return round_up(m < 1 ? 1 : m, PT_TILE); }
+constexpr int64_t postcov_q(int64_t m) { return 2 * postcov_mp(m); }
+
+// Workspace of gp2d_predict_cov: K*ᵀ (n × q) | V = W·K*ᵀ (n × q) | the mean's partial sums
+// ((n / MEAN_SEG) segments × q).
+struct PredictCovWork {
+  size_t Ks = 0, V = 0, pm = 0, total = 0;
+  constexpr PredictCovWork(int64_t n, int64_t m) {
+    const size_t nq = F64 * (size_t)(n > 0 ? n : 0) * (size_t)postcov_q(m);
+    V = nq;
+    pm = 2 * nq;
+    total = pm + predict_partial_bytes(n > 0 ? n : 0, postcov_q(m));
+  }
+  struct Ptrs { double* Ks; double* V; double* pm; };
+  Ptrs at(void* w) const { return {work_at(w, Ks), work_at(w, V), work_at(w, pm)}; }
+};
+constexpr bool predict_cov_work_ok(int64_t n, int64_t m) {
+  const PredictCovWork w(n, m);
+  const size_t nq = F64 * (size_t)n * (size_t)postcov_q(m);
+  return regions_ok({w.Ks, w.V, w.pm, w.total}, {nq, nq, F64 * (size_t)(n / MEAN_SEG + 1) * (size_t)postcov_q(m)});
+}
+static_assert(predict_cov_work_ok(128, 1) && predict_cov_work_ok(384, 130) && predict_cov_work_ok(8192, 4096) &&
+                  postcov_q(1) == 128 && postcov_q(100) == 256 && postcov_q(130) == 384,
+              "predict_cov workspace: regions out of order, overlapping or misaligned");
+
+}  // namespace gp2d

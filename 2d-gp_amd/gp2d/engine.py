@@ -821,6 +821,13 @@ _VAR_MODES = {"latent": N.VAR_LATENT, "gpy": N.VAR_NOISY, "noisy": N.VAR_NOISY, 
               "clipped": N.VAR_CLIPPED}
 
 
+def _f64_fit_args(gp: GPFit, G: torch.Tensor, desc) -> tuple:
+    """What gp2d_predict, gp2d_predict_field and gp2d_predict_cov start with: the factor W and its
+    row stride, α, the training points, the targets, the kernel."""
+    return (_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad, _ptr(G), G.shape[0],
+            ctypes.byref(desc))
+
+
 class Predictor:
     """Reusable predict workspace for one GPFit (chunked over the grid)."""
 
@@ -923,8 +930,7 @@ class Predictor:
                 N.check(L.gp2d_predict_ozaki(*fit_args, int(bool(compute_var)), *out_args, _stream_handle(gp.device)),
                         "gp2d_predict_ozaki")
             return mean, (var if compute_var else None)
-        N.check(L.gp2d_predict(_ptr(gp.W), gp.n, gp.n, _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
-                               _ptr(G), m, ctypes.byref(desc), _VAR_MODES[var_mode], float(gp.noise),
+        N.check(L.gp2d_predict(*_f64_fit_args(gp, G, desc), _VAR_MODES[var_mode], float(gp.noise),
                                int(bool(compute_var)), _ptr(mean), _ptr(var), self.chunk, _ptr(self.work),
                                self.wbytes, _stream_handle(gp.device)), "gp2d_predict")
         return mean, (var if compute_var else None)
@@ -938,13 +944,22 @@ FIELDS = ("divergence", "vorticity")
 _FIELD_CODES = {"divergence": N.FIELD_DIVERGENCE, "vorticity": N.FIELD_VORTICITY}
 
 
-def _field_code(kernel: KernelSpec, field: str) -> int:
-    """The library's code of a derived field, or ValueError for a field or kernel without one."""
+def _require_velocity(kernel: KernelSpec, needs: str, gp: GPFit | None = None, entry: str = ""):
+    """ValueError(needs) unless the kernel is a div-free, curl-free or mixed vector kernel; for a
+    fit, also unless it still has the factor W that `entry` contracts with."""
+    if not kernel.is_vector or kernel._KINDS[kernel.kind] == N.KIND_SCALAR:
+        raise ValueError(needs)
+    if gp is not None and gp.W is None:
+        raise ValueError(f"{entry} needs the fit's factor W = L⁻¹ (this fit keeps only its int8 planes)")
+
+
+def _field_code(kernel: KernelSpec, field: str, gp: GPFit | None = None) -> int:
+    """The library's code of a derived field, or ValueError for a field or kernel without one
+    (or, given the fit to predict it from, a fit without W)."""
     if field not in _FIELD_CODES:
         raise ValueError(f"field must be one of {FIELDS}")
-    if not kernel.is_vector or kernel._KINDS[kernel.kind] == N.KIND_SCALAR:
-        raise ValueError("derived fields need a div-free, curl-free or mixed vector kernel "
-                         "(the scalar kind and the ARD family have none)")
+    _require_velocity(kernel, "derived fields need a div-free, curl-free or mixed vector kernel "
+                              "(the scalar kind and the ARD family have none)", gp, "predict_field")
     return _FIELD_CODES[field]
 
 
@@ -964,9 +979,7 @@ def predict_field(gp: GPFit, xg, field: str, compute_var: bool = True, chunk: in
     Works for fits of either variance engine — the contraction runs on the FP64 engine from the
     fit's W; gp.x, gp.alpha and gp.W share one point order.  ValueError for the scalar kind, the
     ARD family, and a fit without W (a job stream's receiving rank keeps only the int8 planes)."""
-    code = _field_code(gp.kernel, field)
-    if gp.W is None:
-        raise ValueError("predict_field needs the fit's factor W = L⁻¹ (this fit keeps only its int8 planes)")
+    code = _field_code(gp.kernel, field, gp)
     L = N.lib()
     G = _as_points(xg, gp.kernel.input_dim, gp.device)
     m = G.shape[0]
@@ -977,8 +990,7 @@ def predict_field(gp: GPFit, xg, field: str, compute_var: bool = True, chunk: in
     mean = torch.empty(m, dtype=torch.float64, device=gp.device)
     var = torch.empty(m, dtype=torch.float64, device=gp.device) if compute_var else None
     desc = gp.kernel.desc()
-    N.check(L.gp2d_predict_field(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
-                                 _ptr(G), m, ctypes.byref(desc), code, int(bool(compute_var)), _ptr(mean),
+    N.check(L.gp2d_predict_field(*_f64_fit_args(gp, G, desc), code, int(bool(compute_var)), _ptr(mean),
                                  None if var is None else _ptr(var), chunk, _ptr(work), wbytes,
                                  _stream_handle(gp.device)), "gp2d_predict_field")
     return mean, var
@@ -986,11 +998,8 @@ def predict_field(gp: GPFit, xg, field: str, compute_var: bool = True, chunk: in
 
 def _predict_cov_padded(gp: GPFit, xg, diag_add: float):
     """gp2d_predict_cov: (mean (2m,), the padded q × q covariance, m, mp) on the device."""
-    if not gp.kernel.is_vector or gp.kernel._KINDS[gp.kernel.kind] == N.KIND_SCALAR:
-        raise ValueError("the joint covariance needs a div-free, curl-free or mixed vector kernel "
-                         "(the scalar kind and the ARD family are not supported)")
-    if gp.W is None:
-        raise ValueError("predict_cov needs the fit's factor W = L⁻¹ (this fit keeps only its int8 planes)")
+    _require_velocity(gp.kernel, "the joint covariance needs a div-free, curl-free or mixed vector kernel "
+                                 "(the scalar kind and the ARD family are not supported)", gp, "predict_cov")
     L = N.lib()
     G = _as_points(xg, gp.kernel.input_dim, gp.device)
     m = G.shape[0]
@@ -1003,8 +1012,7 @@ def _predict_cov_padded(gp: GPFit, xg, diag_add: float):
     mean = torch.empty(2 * m, dtype=torch.float64, device=gp.device)
     cov = torch.empty((q, q), dtype=torch.float64, device=gp.device)
     desc = gp.kernel.desc()
-    N.check(L.gp2d_predict_cov(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
-                               _ptr(G), m, ctypes.byref(desc), float(diag_add), _ptr(mean), _ptr(cov), q,
+    N.check(L.gp2d_predict_cov(*_f64_fit_args(gp, G, desc), float(diag_add), _ptr(mean), _ptr(cov), q,
                                _ptr(work), wbytes, _stream_handle(gp.device)), "gp2d_predict_cov")
     return mean, cov, m, mp
 

@@ -79,6 +79,39 @@ def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
     assert np.array_equal(mean, mu.cpu().numpy()) and np.array_equal(var, va.cpu().numpy())
 
 
+def test_timing_contract_of_the_predicts():
+    """What bench.py reads through timing_read() after timing_enable(True): the FP64 predict records
+    one launch per chunk (the W·K*ᵀ product) with bd·cv·(bd·N)² flop, none without the variance;
+    predict_field records nothing; predict_cov records the covariance kernel with 2N·(2m)² flop; the
+    int8 predict records one entry per chunk with 2·cv·(2N)² flop.  100 training points, 300 targets,
+    chunk = 128: chunks of 128, 128 and 44."""
+    import predict_cases as PC
+    from gp2d import engine as E
+    ntr, m, xg = PC.NTR, PC.M, PC.targets()
+    gp, gpf, gpo = PC.fit("df"), PC.fit("vorticity"), PC.fit("df", "ozaki")
+    chunks = (128, 128, 44)
+    assert sum(chunks) == m
+    E.timing_enable(True)
+    try:
+        E.timing_read()
+        E.predict(gp, xg, chunk=128)
+        ms, launches, flops = E.timing_read()
+        assert launches == 3 and flops == sum(2 * cv * (2 * ntr) ** 2 for cv in chunks) and ms > 0
+        E.predict(gp, xg, compute_var=False, chunk=128)
+        assert E.timing_read()[1:] == (0, 0.0)
+        E.predict_field(gpf, xg, "vorticity", chunk=128)
+        assert E.timing_read()[1:] == (0, 0.0)
+        E.predict_cov(gp, xg[:PC.COV_M])
+        _, launches, flops = E.timing_read()
+        assert launches == 1 and flops == 2 * ntr * (2 * PC.COV_M) ** 2
+        E.predict(gpo, xg, chunk=128)
+        _, launches, flops = E.timing_read()
+        assert launches == 3 and flops == sum(2 * cv * (2 * ntr) ** 2 for cv in chunks)
+    finally:
+        E.timing_enable(False)
+        E.timing_read()
+
+
 def test_bench_two_ranks_default_contract():
     """The N > 1 default (strong scaling, round-robin fits + factor broadcast) through
     torch.distributed.run with two ranks on the one card (gloo: RCCL refuses two ranks per

@@ -264,6 +264,42 @@ def test_jitchol_retry(variance):
     assert E.fit(ks, x[:60], y[:120], noise=0.01, variance=variance, jitchol=5).extra["jitchol"] == 0.0
 
 
+@pytest.mark.parametrize("case", ["df", "ard", "vorticity", "cov"])
+def test_predict_workspace_of_the_exported_size_is_enough(case):
+    """gp2d_predict (div-free, bd = 2; ARD, bd = 1, n = 128), gp2d_predict_field (mixed kernel,
+    vorticity) and gp2d_predict_cov (m = 100, q = 256) through the raw ABI, each in the first
+    `wbytes` of a buffer whose last MiB holds a sentinel: the exported size is enough (three chunks
+    of 128, 128 and 44 targets), no byte past it is written, and the results are bit for bit the
+    engine's, which allocates by the same exported sizes."""
+    import predict_cases as PC
+    mean, out, tail = PC.raw(case)
+    assert tail.numel() >= 1 << 20 and bool(torch.all(tail == PC.SENTINEL))
+    emean, eout = PC.through_engine(case)
+    assert torch.equal(mean, emean)
+    if case == "cov":
+        m, mp = PC.COV_M, E.padded_points(PC.COV_M)
+        idx = torch.cat([torch.arange(m), mp + torch.arange(m)]).to(out.device)
+        out = out.index_select(0, idx).index_select(1, idx)
+    assert out.shape == eout.shape and torch.equal(out, eout)
+    assert bool(torch.all(torch.isfinite(out)))
+
+
+@pytest.mark.parametrize("compute_var", [True, False])
+@pytest.mark.parametrize("case", ["df", "ard", "vorticity"])
+def test_predict_chunking_changes_no_bit(case, compute_var):
+    """Three chunks (chunk = 128: 128, 128 and 44 targets) against one (chunk = 8192): every output
+    column's sums run in a fixed order that does not depend on its neighbours, so the mean and the
+    variance are the same bits, with and without the variance."""
+    import predict_cases as PC
+    m3, v3, _ = PC.raw(case, chunk=128, compute_var=compute_var)
+    m1, v1, _ = PC.raw(case, chunk=8192, compute_var=compute_var)
+    assert np.array_equal(m3.cpu().numpy(), m1.cpu().numpy())
+    if compute_var:
+        assert np.array_equal(v3.cpu().numpy(), v1.cpu().numpy())
+    else:
+        assert v3 is None and v1 is None
+
+
 _SCHED_CHILD = r'''
 import ctypes, hashlib, json, sys
 import numpy as np, torch

@@ -378,6 +378,46 @@ def test_factor_workspace_sizes_are_the_recorded_ones():
         assert int(L.gp2d_potrf_workspace(n)) == 0 and int(L.gp2d_trtri_batched_workspace(n, 0)) == 0, n
 
 
+def test_predict_workspace_sizes_are_the_recorded_ones():
+    """The FP64 predicts' exported workspace sizes (host functions, no device needed) against values
+    recorded from the library of commit d8ccbf8, before the sizes came from the layout structs of
+    csrc/predict_host.hpp: callers allocate by them, so a layout change must not move them.  (The
+    structs' internal consistency — order, no overlap, alignment — is a static_assert there.)"""
+    from gp2d import _native as N
+    L = N.lib()
+    recorded = [
+        (L.gp2d_predict_workspace, (0, 128, 2), 4096),              # no rows: the two partial rows only
+        (L.gp2d_predict_workspace, (256, 0, 2), 268288),            # chunk < 1 sizes as one tile
+        (L.gp2d_predict_workspace, (256, 64, 2), 268288),           # 8·(256 + 2·3)·128
+        (L.gp2d_predict_workspace, (256, 64, 1), 268288),           # 64 columns round up to 128
+        (L.gp2d_predict_workspace, (256, 100, 2), 536576),          # chunk not a multiple of 64
+        (L.gp2d_predict_workspace, (256, 100, 1), 268288),
+        (L.gp2d_predict_workspace, (128, 128, 1), 135168),
+        (L.gp2d_predict_workspace, (256, 128, 2), 536576),
+        (L.gp2d_predict_workspace, (8192, 8192, 2), 1090781184),    # 8·(8192 + 2·65)·16384
+        (L.gp2d_predict_workspace, (8192, 8192, 1), 545390592),
+        (L.gp2d_predict_workspace, (32768, 8192, 2), 4362338304),
+        (L.gp2d_predict_workspace, (32768, 200, 1), 68161536),
+        (L.gp2d_predict_field_workspace, (0, 128), 2048),
+        (L.gp2d_predict_field_workspace, (256, 0), 268288),
+        (L.gp2d_predict_field_workspace, (256, 128), 268288),
+        (L.gp2d_predict_field_workspace, (256, 100), 268288),
+        (L.gp2d_predict_field_workspace, (8192, 8192), 545390592),
+        (L.gp2d_predict_field_workspace, (32768, 1024), 272646144),
+        (L.gp2d_predict_cov_workspace, (0, 100), 2048),
+        (L.gp2d_predict_cov_workspace, (128, 0), 264192),           # m < 1 sizes as one tile
+        (L.gp2d_predict_cov_workspace, (128, 1), 264192),           # 8·(2·128 + 2)·128
+        (L.gp2d_predict_cov_workspace, (256, 64), 527360),
+        (L.gp2d_predict_cov_workspace, (256, 65), 1054720),         # one point into the second tile
+        (L.gp2d_predict_cov_workspace, (256, 100), 1054720),
+        (L.gp2d_predict_cov_workspace, (384, 130), 2371584),
+        (L.gp2d_predict_cov_workspace, (8192, 4096), 1078001664),
+        (L.gp2d_predict_cov_workspace, (32768, 4096), 4311810048),
+    ]
+    for f, args, want in recorded:
+        assert int(f(*args)) == want, (f.__name__, args)
+
+
 def test_factor_join_mode_is_per_thread_and_restorable():
     """gp2d_factor_join (host state only, no device needed): a negative argument queries, the
     previous mode is returned, and the mode belongs to the calling thread (engine.fit sets and
