@@ -655,11 +655,11 @@ def krige_jobs_sharded(jobs, variance: str = "ozaki", chunk: int = 8192, var_mod
         # this job's status (broadcast with its factor): raises on every rank, and applies the
         # owner's accuracy-guard statistics on every rank (the same decision everywhere) before
         # the predict is queued; the broadcast ran under the previous job's predict
-        gp.check()
-        E.note_guard(stats, gp)
-        main.wait_event(ready)
-        gp.ready_on(main)
-        gp.record_stream(main)
+        # (the guard's stream is the one its fit was made or received on, armed there)
+        (gp, err), = E.take_fits([gp], None, main, ready)
+        if err is not None:
+            raise err
+        E.hand_over(gp, stats, main)
         pred = E._predictor_for(pred, gp, chunk)
         out = predict_shard(pred, E._as_points(xg, spec.input_dim, dev), var_mode=var_mode,
                             compute_var=compute_var, align=align)

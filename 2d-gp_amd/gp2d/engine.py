@@ -1182,78 +1182,37 @@ def krige_jobs(jobs, variance: str = "ozaki", chunk: int = 8192, var_mode: str =
     job's shape."""
     dev = _require_device(device)
     main = torch.cuda.current_stream(dev)
-    it = iter(jobs)
-    if fits_ahead is None:
-        first, it = _peek(it)
-        if first is None:
-            return
-        kernel, x, _, _, xg = first
-        fits_ahead = auto_fits_ahead(kernel, _point_count(x, kernel.input_dim),
-                                     _point_count(xg, kernel.input_dim), variance, compute_var)
-    if int(fits_ahead) <= 0:
-        if batch_fits is None or batch_ahead is None:
-            first, it = _peek(it)
-            if first is None:
-                return
-            kernel, x, xg = first[0], first[1], first[4]
-            ntr = _point_count(x, kernel.input_dim)
-            if batch_fits is None:
-                batch_fits = auto_fit_batch(kernel, ntr, variance)
-            if batch_ahead is None:
-                batch_ahead = auto_batch_ahead(kernel, ntr, _point_count(xg, kernel.input_dim), int(batch_fits),
-                                               variance, compute_var)
-        if int(batch_fits) > 1:
-            yield from _krige_jobs_batched(it, int(batch_fits), variance, chunk, var_mode, compute_var, jitter, dev,
-                                           stats, ahead=bool(batch_ahead))
-        else:
-            yield from _krige_jobs_serial(it, variance, chunk, var_mode, compute_var, jitter, dev, stats)
+    first, it = _peek(iter(jobs))
+    if first is None:
         return
-    k = max(1, int(fits_ahead))
-    sides = [side_stream(dev) for _ in range(k)]
-    prev_sets = N.lib().gp2d_factor_sets(k) if k > 1 else None   # one internal factor set per side stream
-    issued = [0]
+    n_sides, b, targets = _job_schedule(*_job_mode(first, variance, compute_var, fits_ahead, batch_fits, batch_ahead))
+    sides = [side_stream(dev) for _ in range(n_sides)]
+    prev_sets = N.lib().gp2d_factor_sets(n_sides) if n_sides > 1 else None   # one internal factor set per side stream
+    pred = None
 
-    def queue_fit(job):
-        kernel, x, y, noise, _ = job
-        side = sides[issued[0] % k]
-        # one fit in flight: the first has no predict to overlap, so it joins on the host (no
-        # wait left pending on the side stream beside its chain, fit(join=...))
-        join = k == 1 and issued[0] == 0
-        issued[0] += 1
-        side.wait_stream(main)
-        note_fit_issued(stats)
-        with torch.cuda.stream(side):
-            return side, fit(kernel, x, y, noise, jitter=jitter, device=dev, variance=variance, check=False,
-                             join=join)
+    def issue(group, index):
+        s, join = _fit_slot(index, n_sides)
+        side = None if s is None else sides[s]
+        if side is not None:
+            side.wait_stream(main)
+        for _ in group:
+            note_fit_issued(stats)
+        kw = dict(jitter=jitter, device=dev, variance=variance, check=False, join=join)
+        with torch.cuda.stream(side):   # no side stream: the current one
+            if b == 1:
+                kernel, x, y, noise, _ = group[0]
+                return [fit(kernel, x, y, noise, **kw)], side
+            return fit_batch([job[:4] for job in group], **kw), side
 
-    queue = collections.deque()   # (job, side stream, gp) with the fit queued
-
-    def fill(limit):
-        while len(queue) < limit:
-            job = next(it, None)
-            if job is None:
-                return
-            queue.append((job, *queue_fit(job)))
+    def predict(job, gp):
+        nonlocal pred
+        hand_over(gp, stats, main if sides else None)
+        pred, out = _predict_job(pred, gp, job[4], chunk, var_mode, compute_var)
+        return out
 
     try:
-        fill(1)
-        pred = None
-        while queue:
-            if k > 1:
-                fill(k)   # before the predict stream waits for the head job's fit
-            job, side, gp = queue.popleft()
-            # this job's status (LinAlgError, the accuracy guard — which may re-prepare the
-            # planes on `side`) before its predict is queued; the host waits for this fit only,
-            # which ran under the previous job's predict, so the GPU never waits for the host
-            with torch.cuda.stream(side):
-                gp.check()
-            note_guard(stats, gp)
-            main.wait_stream(side)
-            gp.record_stream(main)
-            if k == 1:
-                fill(1)   # the next job's fit, under this job's predict
-            pred, out = _predict_job(pred, gp, job[4], chunk, var_mode, compute_var)
-            yield out
+        yield from _run_schedule(_job_groups(it, b, variance), targets, issue,
+                                 lambda issued: take_fits(*issued, main), predict)
     finally:
         if prev_sets is not None:
             N.lib().gp2d_factor_sets(prev_sets)
@@ -1355,9 +1314,64 @@ def auto_fit_batch(kernel: KernelSpec, n_train: int, variance: str = "ozaki") ->
     return max(1, min(cap, FIT_BATCH_MAX_BYTES // (2 * fit_problem_bytes(n))))
 
 
+def _job_mode(first, variance, compute_var, fits_ahead, batch_fits, batch_ahead):
+    """krige_jobs' (fits_ahead, batch_fits, batch_ahead) for a stream whose first job is `first`:
+    what the caller passed, None replaced by the auto_* rule on that job's shape; a batch only
+    with fits_ahead = 0, batch_ahead only for a batch of more than one fit."""
+    kernel, x, xg = first[0], first[1], first[4]
+    ntr, m = _point_count(x, kernel.input_dim), _point_count(xg, kernel.input_dim)
+    if fits_ahead is None:
+        fits_ahead = auto_fits_ahead(kernel, ntr, m, variance, compute_var)
+    fits_ahead = max(0, int(fits_ahead))
+    if fits_ahead == 0 and batch_fits is None:
+        batch_fits = auto_fit_batch(kernel, ntr, variance)
+    if fits_ahead > 0 or int(batch_fits) <= 1:
+        return fits_ahead, 1, False
+    if batch_ahead is None:
+        batch_ahead = auto_batch_ahead(kernel, ntr, m, int(batch_fits), variance, compute_var)
+    return fits_ahead, int(batch_fits), bool(batch_ahead)
+
+
+def _job_schedule(fits_ahead: int, b: int, batch_ahead: bool):
+    """(side streams, jobs per fit, (before, after_take, after_first)) of a job stream's mode.
+    The targets are queue lengths of _run_schedule: groups issued before the head group is taken,
+    after its hand-over, and after its first predict."""
+    if fits_ahead > 1:
+        # k fits in flight, each queued before the predict stream waits for the job ahead of it, so
+        # consecutive fits also overlap each other (gp2d_potrf draws a factor stream set per side):
+        # config B 3.8e6 points/s with two fits in flight, 2.8–3.3e6 with one
+        # (profiles/r03_ring_depth_E_B_ab.txt)
+        return fits_ahead, 1, (fits_ahead, 0, 0)
+    if fits_ahead == 1:
+        # job i+1's fit under job i's predict: the headline 55.7 vs 61.3 ms per job back to back
+        # (auto_fits_ahead, profiles/r03_problem_sizes.txt)
+        return 1, 1, (1, 1, 0)
+    if batch_ahead:
+        # batch g+1's fit under batch g's predicts, queued after the first of them: config B
+        # 8.8e6 vs 7.8e6 points/s back to back (profiles/r04_batch_ahead_ab.txt)
+        return 1, b, (1, 0, 1)
+    # back to back on the current stream: a small job's fit beside a predict runs ≈ 2.4× longer
+    # (config B 4.19e6 points/s vs 2.8–3.3e6 with one fit in flight; batches of b fits pay the
+    # fit's chain once, profiles/r04_fit_batch.jsonl)
+    return 0, b, (1, 0, 0)
+
+
+def _fit_slot(index: int, n_sides: int):
+    """(side stream, join) of a job stream's index-th issue: the sides in turn, none (the current
+    stream, fit's default join) without sides.  With one side the first fit has no predict to
+    overlap, so it joins on the host: no wait is left pending on the side stream beside its chain
+    (fit(join=...))."""
+    if n_sides == 0:
+        return None, None
+    return index % n_sides, n_sides == 1 and index == 0
+
+
 def _job_groups(jobs, b, variance):
     """Consecutive jobs in groups of up to b with one matrix order (a job of another order starts
     the next group)."""
+    if b == 1:   # one job per fit: no layout to compare, and no job read before it is issued
+        yield from ([job] for job in jobs)
+        return
     group, n0 = [], None
     for job in jobs:
         n1 = fit_layout(job[0], _point_count(job[1], job[0].input_dim), variance)[1]
@@ -1370,74 +1384,69 @@ def _job_groups(jobs, b, variance):
         yield group
 
 
-def _krige_jobs_batched(jobs, b, variance, chunk, var_mode, compute_var, jitter, dev, stats, ahead=False):
-    """Jobs with their fits in batches of up to b jobs of one matrix order (engine.fit_batch),
-    predicted one by one.  ahead=False: each batch's fit, then its predicts, on the current
-    stream.  ahead=True: batch g+1's fit on a side stream under batch g's predicts (queued after
-    batch g's first predict); the first batch, with nothing to overlap, joins on the host."""
-    main = torch.cuda.current_stream(dev)
-    side = side_stream(dev) if ahead else None
-    groups = _job_groups(jobs, b, variance)
+def _run_schedule(groups, targets, issue, take, predict):
+    """A job stream's one loop.  issue(group, index) queues a group's fit and returns what
+    take(issued) needs to hand it over; take returns one (fit, error) per job of the group;
+    predict(job, fit) returns the job's result.  fill(t) issues groups until t are queued, so the
+    three targets say when the next fit is issued (_job_schedule) and nothing else differs between
+    the forms.  An error is raised when its own job is reached."""
+    before, after_take, after_first = targets
+    queue, index = collections.deque(), itertools.count()
 
-    def issue(group, first):
-        for _ in group:
-            note_fit_issued(stats)
-        probs = [(k, x, y, nz) for k, x, y, nz, _ in group]
-        if side is None:
-            return fit_batch(probs, variance=variance, jitter=jitter, device=dev, check=False)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            return fit_batch(probs, variance=variance, jitter=jitter, device=dev, check=False, join=first)
+    def fill(target):
+        while len(queue) < target:
+            group = next(groups, None)
+            if group is None:
+                return
+            queue.append((group, issue(group, next(index))))
 
-    pred = None
-    group = next(groups, None)
-    fits = issue(group, True) if group else None
-    while group:
-        if side is not None:
-            main.wait_stream(side)
-            for gp in fits:
-                gp.record_stream(main)
-        nxt, nfits = None, None
-        # status + accuracy guard of EVERY fit of the batch before the next batch's fit is queued
-        # on `side`: a guard that re-prepares planes then queues that work ahead of the next
-        # batch's factorisation, not behind it (the batch's fits end together, so checking them
-        # all now waits no longer than checking the first); an error raises at its own job
-        errs = []
-        for gp in fits:
-            try:
-                with torch.cuda.stream(side if side is not None else main):
-                    gp.check()
-                errs.append(None)
-            except Exception as e:   # noqa: BLE001 — re-raised when its job is reached
-                errs.append(e)
-        for q, (job, gp) in enumerate(zip(group, fits)):
-            if errs[q] is not None:
-                raise errs[q]
-            note_guard(stats, gp)
-            if side is not None:
-                gp.ready_on(main)   # only the guard's own work: `side` may carry the next batch's fit
-                gp.record_stream(main)
-            pred, out = _predict_job(pred, gp, job[4], chunk, var_mode, compute_var)
-            if q == 0 and side is not None:   # the next batch's fit under this batch's predicts
-                nxt = next(groups, None)
-                nfits = issue(nxt, False) if nxt else None
+    while True:
+        fill(before)
+        if not queue:
+            return
+        group, issued = queue.popleft()
+        taken = take(issued)
+        fill(after_take)
+        for q, (job, (gp, err)) in enumerate(zip(group, taken)):
+            if err is not None:
+                raise err
+            out = predict(job, gp)
+            if q == 0:
+                fill(after_first)
             yield out
-        if side is None:
-            nxt = next(groups, None)
-            nfits = issue(nxt, False) if nxt else None
-        group, fits = nxt, nfits
 
 
-def _krige_jobs_serial(jobs, variance, chunk, var_mode, compute_var, jitter, dev, stats):
-    pred = None
-    for job in jobs:
-        kernel, x, y, noise, xg = job
-        note_fit_issued(stats)
-        gp = fit(kernel, x, y, noise, jitter=jitter, device=dev, variance=variance, check=False)
-        gp.check()   # status + accuracy guard before the predict
-        note_guard(stats, gp)
-        pred, out = _predict_job(pred, gp, xg, chunk, var_mode, compute_var)
-        yield out
+def take_fits(fits, stream, main, ready=None):
+    """Hand a group of check=False fits over to the predict stream `main`: every fit's status and
+    accuracy guard (GPFit.check) under `stream`, the one they were issued on (None: the current
+    one), so a guard that re-prepares planes queues that work there — the host waits for these
+    fits only, which ran under the previous predicts, never the GPU for the host.  Then, the fits
+    having run elsewhere, `main` waits for `ready` (an event recorded after them) or else for
+    `stream`: by now that stream holds this group's fits and their guards' work and nothing later,
+    because no schedule issues the next group before the head has been taken.  Returns one (fit,
+    error or None) per fit; the caller raises an error at its own job."""
+    taken = []
+    for gp in fits:
+        try:
+            with torch.cuda.stream(stream):
+                gp.check()
+            taken.append((gp, None))
+        except Exception as e:   # noqa: BLE001 — re-raised when its job is reached
+            taken.append((gp, e))
+    if ready is not None:
+        main.wait_event(ready)
+    elif stream is not None:
+        main.wait_stream(stream)
+    return taken
+
+
+def hand_over(gp: GPFit, stats: dict | None, main=None):
+    """A taken fit's last step before its predict: the guard's decision into `stats`, and — main:
+    the predict stream, when the fit ran on another — the guard's own work and the allocator's
+    bookkeeping on `main`."""
+    note_guard(stats, gp)
+    if main is not None:
+        gp.ready_on(main).record_stream(main)
 
 
 # ------------------------------------------------------------------ hyperparameters

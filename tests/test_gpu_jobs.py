@@ -63,6 +63,24 @@ def test_krige_jobs_empty():
     assert list(E.krige_jobs([])) == []
 
 
+@pytest.mark.parametrize("ahead,batch,bahead,issued", [(0, 1, False, 1), (1, None, None, 2), (2, None, None, 2),
+                                                       (0, 2, True, 4), (0, 2, False, 2)])
+def test_krige_jobs_abandoned_after_the_first_result(ahead, batch, bahead, issued):
+    """A consumer that takes one result and closes the stream: only the fits the schedule had
+    queued by then were issued, and the factor stream sets are as they were before."""
+    L = E.N.lib()
+    sets = L.gp2d_factor_sets(0)
+    stats = {}
+    gen = E.krige_jobs([_job(11, 300, 8, "df")] * 6, variance="ozaki", chunk=1024, stats=stats, fits_ahead=ahead,
+                       batch_fits=batch, batch_ahead=bahead)
+    m, v = next(gen)
+    gen.close()
+    torch.cuda.synchronize()
+    assert torch.isfinite(m).all() and torch.isfinite(v).all()
+    assert stats["fits_issued"] == issued
+    assert L.gp2d_factor_sets(0) == sets
+
+
 @pytest.mark.parametrize("join", [False, True])
 def test_fit_join_modes_same_bits_on_a_side_stream(join):
     """fit(join=...) only moves the host wait (gp2d_factor_join): W, α and the predictions are

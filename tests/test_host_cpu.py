@@ -533,3 +533,103 @@ def test_release_build_rejects_measurement_overrides():
     norel = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-E", "-o", os.devnull, lib_src],
                            capture_output=True, text=True)
     assert norel.returncode != 0 and "GP2D_RELEASE" in norel.stderr
+
+
+# ------------------------------------------------------------------ the job stream's one loop
+def _fake_jobs(orders):
+    """Job tuples whose matrix order follows `orders` (training point counts), numbered in xg."""
+    from gp2d import engine as E
+    spec = E.KernelSpec(kind="df")
+    return [(spec, np.zeros((n, 2)), None, 0.0, j) for j, n in enumerate(orders)]
+
+
+def _traced_stream(fits_ahead, b, batch_ahead, orders, fail=()):
+    """engine._run_schedule over recording fakes: (generator, trace).  I<jobs>@<side><j for a
+    joined fit> = issue, T<jobs> = take, P<job> = predict; `fail`: jobs whose take reports an error."""
+    from gp2d import engine as E
+    n_sides, b, targets = E._job_schedule(fits_ahead, b, batch_ahead)
+    trace = []
+
+    def ids(group):
+        return ",".join(str(job[4]) for job in group)
+
+    def issue(group, index):
+        side, join = E._fit_slot(index, n_sides)
+        trace.append(f"I{ids(group)}@{'-' if side is None else side}{'j' if join else ''}")
+        assert (join is None) == (n_sides == 0)
+        return group
+
+    def take(group):
+        trace.append(f"T{ids(group)}")
+        return [(job[4], KeyError(job[4]) if job[4] in fail else None) for job in group]
+
+    def predict(job, fit):
+        assert fit == job[4]
+        trace.append(f"P{fit}")
+        return fit
+
+    def jobs():   # nothing is read before the first next()
+        trace.append("read")
+        yield from _fake_jobs(orders)
+    return E._run_schedule(E._job_groups(jobs(), b, "ozaki"), targets, issue, take, predict), trace
+
+
+@pytest.mark.parametrize("mode,orders,expected", [
+    ((0, 1, False), [300] * 3, "I0@- T0 P0 I1@- T1 P1 I2@- T2 P2"),
+    ((1, 1, False), [300] * 3, "I0@0j T0 I1@0 P0 T1 I2@0 P1 T2 P2"),
+    ((2, 1, False), [300] * 4, "I0@0 I1@1 T0 P0 I2@0 T1 P1 I3@1 T2 P2 T3 P3"),
+    ((3, 1, False), [300] * 4, "I0@0 I1@1 I2@2 T0 P0 I3@0 T1 P1 T2 P2 T3 P3"),
+    ((0, 2, True), [300] * 5, "I0,1@0j T0,1 P0 I2,3@0 P1 T2,3 P2 I4@0 P3 T4 P4"),
+    ((0, 2, False), [300] * 5, "I0,1@- T0,1 P0 P1 I2,3@- T2,3 P2 P3 I4@- T4 P4"),
+    # a job of another matrix order ends a group early
+    ((0, 3, False), [300, 300, 700, 300], "I0,1@- T0,1 P0 P1 I2@- T2 P2 I3@- T3 P3"),
+    ((0, 2, True), [300, 700, 700, 700], "I0@0j T0 P0 I1,2@0 T1,2 P1 I3@0 P2 T3 P3"),
+])
+def test_job_schedule_event_sequences(mode, orders, expected):
+    """The issue / take / predict order of every form of engine.krige_jobs, with the side stream
+    and join flag of each issue: one fit in flight refills after the hand-over, k > 1 before it,
+    batch_ahead after the batch's first predict, back to back never ahead."""
+    gen, trace = _traced_stream(*mode, orders)
+    assert trace == []                                   # lazy: not even a job read
+    assert list(gen) == list(range(len(orders)))
+    assert " ".join(t for t in trace if t != "read") == expected
+    assert trace[0] == "read"
+
+
+@pytest.mark.parametrize("mode,issued", [((0, 1, False), 1), ((1, 1, False), 2), ((2, 1, False), 2),
+                                         ((0, 2, True), 4), ((0, 2, False), 2)])
+def test_job_schedule_abandoned_after_the_first_result(mode, issued):
+    gen, trace = _traced_stream(*mode, [300] * 6)
+    assert next(gen) == 0
+    gen.close()
+    before = list(trace)
+    assert list(gen) == [] and trace == before
+    assert sum(len(t[1:].split("@")[0].split(",")) for t in trace if t[0] == "I") == issued
+
+
+@pytest.mark.parametrize("mode", [(0, 2, False), (0, 2, True)])
+def test_job_schedule_raises_an_error_at_its_own_job(mode):
+    gen, trace = _traced_stream(*mode, [300] * 4, fail={1})
+    assert next(gen) == 0
+    with pytest.raises(KeyError):
+        next(gen)
+    assert [t for t in trace if t[0] == "P"] == ["P0"]
+
+
+def test_job_mode_matches_the_bench_line():
+    """engine._job_mode resolves (fits_ahead, batch_fits, batch_ahead) as bench.job_stream_shape
+    reports them, for the automatic values and every forced combination."""
+    import itertools
+    import types
+    import bench
+    from gp2d import engine as E
+    df, mixed = E.KernelSpec(kind="df"), E.KernelSpec(kind="mixed", ratio=0.5)
+    for spec, ntrain, m in [(df, 4096, 256 ** 2), (df, 1024, 128 ** 2), (mixed, 16384, 512 ** 2)]:
+        first = (spec, np.zeros((ntrain, 2)), None, 0.0, np.zeros((m, 2)))
+        combos = [(None, None, None)] + list(itertools.product((0, 1, 2), (None, 1, 2), (None, False, True)))
+        for fa, bf, ba in combos:
+            args = types.SimpleNamespace(ntrain=ntrain, variance="ozaki", fits_ahead=fa, batch_fits=bf, batch_ahead=ba)
+            want = bench.job_stream_shape(args, spec, m, "engine.krige_jobs")
+            got = E._job_mode(first, "ozaki", True, fa, bf, ba)
+            assert got == (want["fits_ahead"], want["batch_fits"], want["batch_ahead"]), (ntrain, m, fa, bf, ba)
+    assert E._job_mode(first, "ozaki", True, None, None, None) == (1, 1, False)
