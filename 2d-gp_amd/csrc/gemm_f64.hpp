@@ -10,6 +10,8 @@
 //   * predict variance V = L⁻¹·K*ᵀ with the column sum-of-squares fused in the
 //     epilogue (NN, a_lower, EPI_COLSQ) — replaces Ks·Ki·Ksᵀ (GP_laser.py:129)
 //     and solve_triangular+einsum (_gpr.py:454-475).
+//   * the gradient predict's V = L⁻¹·Cᵀ with the 4 × 4 Gram per target fused in the epilogue
+//     (NN, a_lower, EPI_COLGRAM; grad.hpp)
 //
 // MFMA f64 lane maps (verified on MI355X, tools/microbench/f64_rates.hip):
 //   A: lane l holds A[l&15][l>>4]; B: lane l holds B[l>>4][l&15];
@@ -31,7 +33,8 @@ constexpr int A_TILE = GBM * AS;                                            // 2
 constexpr int B_TILE = (GBK * BS_NN > GBN * BS_NT) ? GBK * BS_NN : GBN * BS_NT;  // 2304
 constexpr int STAGE = A_TILE + B_TILE;
 
-enum { EPI_STORE = 0, EPI_COLSQ = 1 };
+enum { EPI_STORE = 0, EPI_COLSQ = 1, EPI_COLGRAM = 2 };
+constexpr int EPI_COLGRAM_PAIRS = 10;   // entries (a ≤ b) of a 4 × 4 Gram
 
 struct GemmParams {
   const double* A; int64_t lda; int64_t sA;   // M×K row-major
@@ -46,7 +49,8 @@ struct GemmParams {
   int rev_rows;  // dispatch heavy (large i0) row blocks first (a_lower)
   int xcd_cols;  // 1-D grid: groups of 8 column tiles × all row blocks, column tile = XCD label
   int cols_first;  // 1-D grid, column blocks slow and ascending: heavy-first order for b_lower
-  double* P; int64_t ldp; int64_t sP;         // EPI_COLSQ partials [M/BM][N]
+  double* P; int64_t ldp; int64_t sP;         // EPI_COLSQ partials [M/BM][N]; EPI_COLGRAM partials
+                                              // [M/BM][10][N/4], ldp = 10·N/4
   // Block-cyclic column tiles (the distributed factor, dfact.hpp): with jgrp > 0, column tile
   // bj sits jt = (bj / jgrp)·jgrp·jstep + bj % jgrp tiles from C's (and op(B)'s) first column
   // tile — groups of jgrp consecutive tiles, one group every jstep groups (a rank's super-
@@ -249,6 +253,40 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams p) {
       const double none[4][4] = {};
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) cstore(mi, none);
+    }
+  } else if constexpr (EPI == EPI_COLGRAM) {
+    // 4 × 4 Gram per target of this 128-row slab of V (grad.hpp): a lane's four column
+    // accumulators ni = 0..3 are the four components of one target (columns 16 apart inside a
+    // 64-column group), so the ten sums Σ_rows v_a·v_b, a ≤ b, are in-lane; then EPI_COLSQ's
+    // reduction in its order: lanes l, l^16, l^32, l^48 -> the two wave rows.
+    // Partials P[bi][pair][target]: the tile's 2 × 16 targets start at target j0 / 4.
+    double* red = smem;  // [2 wave rows][2 groups][10][16]
+    constexpr int NP = EPI_COLGRAM_PAIRS;
+    double s[NP];
+    int pair = 0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = a; b < 4; ++b, ++pair) {
+        double t = 0.0;
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) t += acc[mi][a][r] * acc[mi][b][r];
+        t += __shfl_xor(t, 16);
+        t += __shfl_xor(t, 32);
+        s[pair] = t;
+      }
+    if (lane < 16) {
+#pragma unroll
+      for (int q = 0; q < NP; ++q) red[((wr * 2 + wc) * NP + q) * 16 + lane] = s[q];
+    }
+    __syncthreads();
+    const int64_t tpad = p.N / 4;   // targets of the chunk: the pair stride
+    double* __restrict__ P = p.P + z * p.sP + (int64_t)bi * p.ldp + j0 / 4;
+    for (int e = tid; e < 2 * NP * 16; e += 256) {
+      const int g = e / (NP * 16), q = (e / 16) % NP, l = e & 15;
+      P[q * tpad + g * 16 + l] = red[e] + red[2 * NP * 16 + e];
     }
   } else {
     // column sums of squares of this 128-row slab of V, combined in a fixed order:

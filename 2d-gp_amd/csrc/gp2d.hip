@@ -12,6 +12,7 @@
 #include "factor.hpp"
 #include "predict.hpp"
 #include "fields.hpp"
+#include "grad.hpp"
 #include "postcov.hpp"
 #include "predict_host.hpp"
 #include "ozaki.hpp"
@@ -1041,43 +1042,61 @@ static GemmParams wk_gemm_params(const double* W, int64_t ldw, int64_t n, const 
   return p;
 }
 
-// What differs between the chunked predicts: components per target, the variance's terms, whether
+// What differs between the chunked predicts: columns per target, the variance's terms, whether
 // the product goes to the timing hooks, and the chunk's cross-covariance — assemble(the chunk's
 // targets, valid count, padded count, out) writes K*ᵀ (n × bd·cp: rows = training components,
-// columns = target components).
+// columns = target components).  gram (the gradient predict, bd = 4 columns per target in grad.hpp's
+// layout): the product's epilogue is EPI_COLGRAM into ten partials per target in place of Σ v² per
+// column, and the finalize is grad_finalize_kernel with the 4 × 4 prior.
 struct ChunkedPredict {
   int bd;
-  double prior, add = 0.0;
+  double prior = 0.0, add = 0.0;
   int clip = 0;
   bool timed = false;
   std::function<int(const double* xg, int64_t cv, int64_t cp, double* Ks)> assemble;
+  bool gram = false;
+  GradPrior prior4{};
 };
 
 // One chunked predict over the m targets (dim coordinates each): per chunk assemble, mean partials,
-// Σ v² partials of W·K*ᵀ if the variance is asked for, finalize.
+// Σ v² (or Gram) partials of W·K*ᵀ if the variance is asked for, finalize.  Ks, pm, P: the chunk's
+// cross-covariance, the mean's partials and the product's partials in the caller's workspace.
 static int predict_chunks(const ChunkedPredict& v, const double* W, int64_t n, int64_t ldw, const double* alpha,
                           int64_t ntr, const double* xg, int dim, int64_t m, int compute_var, double* mean,
-                          double* var, int64_t chunk, void* work, hipStream_t s) {
+                          double* var, int64_t chunk, double* Ks, double* pm, double* P, hipStream_t s) {
   static_assert(GBN == 2 * PT_TILE, "a chunk's bd·cp columns fill whole GEMM column tiles");
-  const auto [Ks, pm, P] = PredictWork(n, v.bd * chunk).at(work);
   const int64_t nseg = predict_segments(n);
   for (int64_t c0 = 0; c0 < m; c0 += chunk) {
     const int64_t cv = std::min<int64_t>(chunk, m - c0);
-    const int64_t cp = round_up(cv, GBN / v.bd);
+    const int64_t cp = round_up(cv, std::max<int64_t>(PT_TILE, GBN / v.bd));   // whole point tiles (grad: 16-groups)
     const int64_t ncols = v.bd * cp;
     GP2D_CHECK(v.assemble(xg + c0 * dim, cv, cp, Ks));
     GP2D_CHECK(launch_mean_partials(Ks, ncols, n, alpha, pm, s));
     if (compute_var) {
       GemmParams p = wk_gemm_params(W, ldw, n, Ks, ncols);
-      p.P = P; p.ldp = ncols;
+      p.P = P; p.ldp = v.gram ? GRAD_NPAIR * cp : ncols;
       const double nv = (double)v.bd * (double)ntr;  // algorithmic order (valid points)
       TimedLaunch t(s, (double)v.bd * (double)cv * nv * nv, v.timed);  // 2·(2N)² per point (vector2d)
-      GP2D_CHECK((launch_gemm<false, EPI_COLSQ>(p, 1, s)));
+      GP2D_CHECK(v.gram ? (launch_gemm<false, EPI_COLGRAM>(p, 1, s)) : (launch_gemm<false, EPI_COLSQ>(p, 1, s)));
     }
-    GP2D_CHECK(launch_finalize({pm, nseg, P, nseg, ncols, cp, cv, c0, m, v.prior, v.add, v.clip, compute_var, mean,
-                                var, nullptr}, s));
+    if (v.gram) {
+      grad_finalize_kernel<<<(unsigned)((cv + 63) / 64), 64, 0, s>>>(pm, P, nseg, cp, cv, c0, v.prior4, compute_var,
+                                                                      mean, var);
+      GP2D_CHECK(check_launch("grad_finalize_kernel"));
+    } else {
+      GP2D_CHECK(launch_finalize({pm, nseg, P, nseg, ncols, cp, cv, c0, m, v.prior, v.add, v.clip, compute_var, mean,
+                                  var, nullptr}, s));
+    }
   }
   return 0;
+}
+
+// gp2d_predict's and gp2d_predict_field's carve of their shared layout
+static int predict_chunks(const ChunkedPredict& v, const double* W, int64_t n, int64_t ldw, const double* alpha,
+                          int64_t ntr, const double* xg, int dim, int64_t m, int compute_var, double* mean,
+                          double* var, int64_t chunk, void* work, hipStream_t s) {
+  const auto [Ks, pm, P] = PredictWork(n, v.bd * chunk).at(work);
+  return predict_chunks(v, W, n, ldw, alpha, ntr, xg, dim, m, compute_var, mean, var, chunk, Ks, pm, P, s);
 }
 
 size_t gp2d_predict_workspace(int64_t n, int64_t chunk, int bd) {
@@ -1166,6 +1185,50 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
     return check_launch("assemble_field_kernel");
   };
   return predict_chunks(v, W, n, ldw, alpha, ntr, xg, point_dim(k), m, compute_var, mean, var, chunk, work, s);
+}
+
+// ------------------------------------------------------- PREDICT (velocity gradient tensor)
+int gp2d_grad_prior_cov(const gp2d_kernel_t* k, double out[16]) {
+  if (out == nullptr) {
+    set_error("grad_prior_cov: out is NULL");
+    return -2;
+  }
+  for (int i = 0; i < 16; ++i) out[i] = std::nan("");
+  GP2D_CHECK(validate_kernel(k));
+  GP2D_REQUIRE(field_kernel_ok(k), "grad_prior_cov: div-free, curl-free or mixed vector kernels only");
+  grad_prior_cov(k, out);
+  return 0;
+}
+
+size_t gp2d_predict_grad_workspace(int64_t n, int64_t chunk) { return PredictGradWork(n, chunk).total; }
+
+int gp2d_predict_grad(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
+                      int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, int compute_cov,
+                      double* mean, double* cov, int64_t chunk, void* work, size_t work_bytes, void* stream) {
+  GP2D_CHECK(validate_kernel(k));
+  GP2D_REQUIRE(field_kernel_ok(k), "predict_grad: div-free, curl-free or mixed vector kernels only");
+  GP2D_REQUIRE(n == 2 * ntr_pad, "predict_grad: n must equal 2 × ntr_pad");
+  GP2D_REQUIRE(n % NB == 0 && n > 0, "predict_grad: n must be a positive multiple of 128");
+  GP2D_REQUIRE(ntr >= 0 && ntr <= ntr_pad && ldw >= n, "predict_grad: bad point count or ldw");
+  GP2D_REQUIRE(chunk > 0 && chunk % PT_TILE == 0, "predict_grad: chunk must be a positive multiple of 64");
+  GP2D_REQUIRE(n < (int64_t)1 << 30 && chunk < (int64_t)1 << 28, "predict_grad: n or chunk out of range");
+  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_predict_grad_workspace(n, chunk),
+               "predict_grad: workspace too small");
+  if (m <= 0) return 0;
+  hipStream_t s = S(stream);
+  const GradParams gp = make_grad_params(k);
+  // four columns per target in grad.hpp's layout; the 4 × 4 prior, no noise, no clipping; untimed
+  ChunkedPredict v;
+  v.bd = GRAD_NC;
+  v.gram = true;
+  grad_prior_cov(k, v.prior4.p);
+  v.assemble = [=](const double* xc, int64_t cv, int64_t cp, double* C) {
+    const dim3 grid((unsigned)(cp / 64), (unsigned)((ntr_pad + ASM_ROWS - 1) / ASM_ROWS));
+    assemble_grad_kernel<<<grid, 256, 0, s>>>(xtr, ntr, ntr_pad, xc, cv, cp, gp, C);
+    return check_launch("assemble_grad_kernel");
+  };
+  const auto [C, pm, G] = PredictGradWork(n, chunk).at(work);
+  return predict_chunks(v, W, n, ldw, alpha, ntr, xg, point_dim(k), m, compute_cov, mean, cov, chunk, C, pm, G, s);
 }
 
 // ------------------------------------------------- PREDICT (joint posterior covariance)

@@ -1,5 +1,5 @@
-// predict_host.hpp — the two workspace layouts of the FP64 predicts (gp2d_predict and
-// gp2d_predict_field; gp2d_predict_cov), as byte-offset tables.  gp2d.hip takes every FP64 predict
+// predict_host.hpp — the three workspace layouts of the FP64 predicts (gp2d_predict and
+// gp2d_predict_field; gp2d_predict_grad; gp2d_predict_cov), as byte-offset tables.  gp2d.hip takes every FP64 predict
 // workspace size it reports and every pointer it carves from here; nothing else knows the layouts
 // (the kernels in predict.hpp, gemm_f64.hpp and postcov.hpp get plain pointers).
 #pragma once
@@ -51,6 +51,33 @@ static_assert(predict_work_ok(128, 128) && predict_work_ok(256, 256) && predict_
                   predict_sized_cols(8192, 2) == 16384 && predict_sized_cols(64, 1) == 128 &&
                   predict_sized_cols(0, 2) == 128 && predict_sized_cols(100, 2) == 256,
               "predict workspace: regions out of order, overlapping or misaligned");
+
+// Workspace of gp2d_predict_grad: C = cov(observations, ∇f) of a chunk (n × 4·chunk, grad.hpp's
+// column layout) | the mean's partial sums (4·chunk columns) | the Gram partial sums (10 per target
+// and 128-row segment, the EPI_COLGRAM epilogue).  chunk is a positive multiple of 64, so a chunk's
+// padded target count never exceeds it; chunk < 1 sizes as one tile.
+struct PredictGradWork {
+  size_t C = 0, pm = 0, G = 0, total = 0;
+  constexpr PredictGradWork(int64_t n, int64_t chunk) {
+    const int64_t cp = round_up(chunk < 1 ? 1 : chunk, PT_TILE);
+    pm = F64 * (size_t)(n > 0 ? n : 0) * (size_t)(4 * cp);
+    G = pm + predict_partial_bytes(n > 0 ? n : 0, 4 * cp);
+    total = G + predict_partial_bytes(n > 0 ? n : 0, EPI_COLGRAM_PAIRS * cp);
+  }
+  struct Ptrs { double* C; double* pm; double* G; };
+  Ptrs at(void* w) const { return {work_at(w, C), work_at(w, pm), work_at(w, G)}; }
+};
+constexpr bool predict_grad_work_ok(int64_t n, int64_t chunk) {
+  const PredictGradWork w(n, chunk);
+  const size_t seg = (size_t)(n / 128 + 1);
+  return regions_ok({w.C, w.pm, w.G, w.total},
+                    {F64 * (size_t)n * (size_t)(4 * chunk), F64 * seg * (size_t)(4 * chunk),
+                     F64 * seg * (size_t)(10 * chunk)}) &&
+         w.total == F64 * (size_t)chunk * (size_t)(4 * n + 14 * (n / 128 + 1));
+}
+static_assert(predict_grad_work_ok(128, 64) && predict_grad_work_ok(384, 256) && predict_grad_work_ok(8192, 8192) &&
+                  PredictGradWork(256, 0).total == PredictGradWork(256, 64).total,
+              "predict_grad workspace: regions out of order, overlapping or misaligned");
 
 // Padded target count and matrix order of gp2d_predict_cov.
 constexpr int64_t postcov_mp(int64_t m) { return round_up(m < 1 ? 1 : m, PT_TILE); }

@@ -29,6 +29,7 @@ EXPORTS = (
     "gp2d_trtri_batched",
     "gp2d_potrs_workspace", "gp2d_potrs_inv", "gp2d_predict_workspace", "gp2d_predict",
     "gp2d_field_prior_var", "gp2d_predict_field_workspace", "gp2d_predict_field",
+    "gp2d_grad_prior_cov", "gp2d_predict_grad_workspace", "gp2d_predict_grad",
     "gp2d_predict_cov_workspace", "gp2d_predict_cov",
     "gp2d_ozaki_nmod", "gp2d_ozaki_wres_bytes", "gp2d_ozaki_prepare", "gp2d_ozaki_prepare_async", "gp2d_ozaki_prepare_packed",
     "gp2d_ozaki_guard_workspace", "gp2d_ozaki_guard", "gp2d_ozaki_error_model", "gp2d_ozaki_guard_bits",
@@ -107,6 +108,9 @@ _SIGS = {
     "gp2d_field_prior_var": (_D, [_KP, _I]),
     "gp2d_predict_field_workspace": (_SZ, [_I64, _I64]),
     "gp2d_predict_field": (_I, [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _KP, _I, _I, _P, _P, _I64, _P, _SZ, _P]),
+    "gp2d_grad_prior_cov": (_I, [_KP, ctypes.POINTER(_D)]),
+    "gp2d_predict_grad_workspace": (_SZ, [_I64, _I64]),
+    "gp2d_predict_grad": (_I, [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _KP, _I, _P, _P, _I64, _P, _SZ, _P]),
     "gp2d_predict_cov_workspace": (_SZ, [_I64, _I64]),
     "gp2d_predict_cov": (_I, [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _KP, _D, _P, _P, _I64, _P, _SZ, _P]),
     "gp2d_ozaki_nmod": (_I, [_I64]),

@@ -181,6 +181,16 @@ class KernelSpec:
         field vanishes by kind.  ValueError for the scalar kind and the ARD family."""
         return float(N.lib().gp2d_field_prior_var(ctypes.byref(self.desc()), _field_code(self, field)))
 
+    def grad_prior_cov(self) -> np.ndarray:
+        """(4, 4) prior covariance of the velocity gradient tensor at one point, components
+        GRADIENT_COMPONENTS (gp2d_grad_prior_cov): singular along the divergence for 'df' and along
+        the vorticity for 'cf'.  ValueError for the scalar kind and the ARD family."""
+        _require_velocity(self, "the velocity gradient needs a div-free, curl-free or mixed vector kernel "
+                                "(the scalar kind and the ARD family have none)")
+        out = (ctypes.c_double * 16)()
+        N.check(N.lib().gp2d_grad_prior_cov(ctypes.byref(self.desc()), out), "gp2d_grad_prior_cov")
+        return np.array(out, dtype=np.float64).reshape(4, 4)
+
 
 def padded_points(n: int) -> int:
     return int(N.lib().gp2d_padded_points(int(n)))
@@ -994,6 +1004,85 @@ def predict_field(gp: GPFit, xg, field: str, compute_var: bool = True, chunk: in
                                  None if var is None else _ptr(var), chunk, _ptr(work), wbytes,
                                  _stream_handle(gp.device)), "gp2d_predict_field")
     return mean, var
+
+
+GRADIENT_COMPONENTS = ("du_dx", "du_dy", "dv_dx", "dv_dy")
+# the linear diagnostics as aᵀ∇f on (du_dx, du_dy, dv_dx, dv_dy)
+_LINEAR_DIAGNOSTICS = {"divergence": (1.0, 0.0, 0.0, 1.0), "vorticity": (0.0, -1.0, 1.0, 0.0),
+                       "normal_strain": (1.0, 0.0, 0.0, -1.0), "shear_strain": (0.0, 1.0, 1.0, 0.0)}
+# Okubo–Weiss σ_n² + σ_s² − ζ² = (g0 − g3)² + 4·g1·g2 = gᵀAg
+_OW_MATRIX = ((1.0, 0.0, 0.0, -1.0), (0.0, 0.0, 2.0, 0.0), (0.0, 2.0, 0.0, 0.0), (-1.0, 0.0, 0.0, 1.0))
+DIAGNOSTICS = tuple(_LINEAR_DIAGNOSTICS) + ("okubo_weiss",)
+
+
+def predict_gradient(gp: GPFit, xg, compute_cov: bool = True, chunk: int = 8192):
+    """Posterior mean and covariance of the velocity gradient tensor at the points xg: device
+    tensors (mean (m, 4), cov (m, 4, 4)), cov None if not asked.
+
+    Components GRADIENT_COMPONENTS = (∂f1/∂x1, ∂f1/∂x2, ∂f2/∂x1, ∂f2/∂x2) for points (x1, x2) and
+    components (f1, f2) = the first and second half of the observations — (∂u/∂x, ∂u/∂y, ∂v/∂x,
+    ∂v/∂y) with Krig.predict_grid's conventions; predict_field's caveat for (Y, X) callers stands.
+    cov[j] is the joint posterior covariance of the four at point j (exactly symmetric), not
+    between points: what flow_diagnostics needs for the variance of every linear diagnostic and
+    the moments of the Okubo–Weiss parameter.  One product of the velocity predict's kind on four
+    columns per point, the 4 × 4 Gram formed in its epilogue (gp2d_predict_grad).
+    No noise or clipping mode: a gradient is never observed.
+
+    Works for fits of either variance engine, like predict_field.  ValueError for the scalar kind,
+    the ARD family, and a fit without W."""
+    _require_velocity(gp.kernel, "the velocity gradient needs a div-free, curl-free or mixed vector kernel "
+                                 "(the scalar kind and the ARD family have none)", gp, "predict_gradient")
+    L = N.lib()
+    G = _as_points(xg, gp.kernel.input_dim, gp.device)
+    m = G.shape[0]
+    chunk = max(64, (int(chunk) + 63) // 64 * 64)
+    chunk = min(chunk, max(64, (m + 63) // 64 * 64))   # no workspace beyond the points there are
+    wbytes = int(L.gp2d_predict_grad_workspace(gp.n, chunk))
+    work = _workspace(wbytes, gp.device)
+    mean = torch.empty((m, 4), dtype=torch.float64, device=gp.device)
+    cov = torch.empty((m, 4, 4), dtype=torch.float64, device=gp.device) if compute_cov else None
+    desc = gp.kernel.desc()
+    N.check(L.gp2d_predict_grad(*_f64_fit_args(gp, G, desc), int(bool(compute_cov)), _ptr(mean),
+                                None if cov is None else _ptr(cov), chunk, _ptr(work), wbytes,
+                                _stream_handle(gp.device)), "gp2d_predict_grad")
+    return mean, cov
+
+
+def flow_diagnostics(mean, cov=None, names=DIAGNOSTICS) -> dict:
+    """Kinematic diagnostics of the flow from its gradient tensor: {name: (mean, var)} for
+    predict_gradient's (mean (..., 4), cov (..., 4, 4)), torch tensors or numpy arrays alike; var
+    is None without cov.
+
+    'divergence' g0 + g3, 'vorticity' g2 − g1, 'normal_strain' g0 − g3 and 'shear_strain' g2 + g1
+    are linear: aᵀμ and aᵀΣa.  'okubo_weiss' σ_n² + σ_s² − ζ² = gᵀAg is quadratic; for Gaussian g
+    its mean is μᵀAμ + tr(AΣ) (μᵀAμ without cov) and its variance 2·tr(AΣAΣ) + 4·μᵀAΣAμ."""
+    is_torch = isinstance(mean, torch.Tensor)
+
+    def const(rows):
+        if is_torch:
+            return torch.tensor(rows, dtype=mean.dtype, device=mean.device)
+        return np.asarray(rows, dtype=np.float64)
+
+    out = {}
+    for name in names:
+        if name in _LINEAR_DIAGNOSTICS:
+            a = const(_LINEAR_DIAGNOSTICS[name])
+            out[name] = (mean @ a, None if cov is None else ((cov @ a) * a).sum(-1))
+        elif name == "okubo_weiss":
+            A = const(_OW_MATRIX)
+            Am = mean @ A                                   # A symmetric: (Aμ)ᵀ
+            mu = (Am * mean).sum(-1)
+            if cov is None:
+                out[name] = (mu, None)
+                continue
+            AS = A @ cov
+            tr1 = AS[..., 0, 0] + AS[..., 1, 1] + AS[..., 2, 2] + AS[..., 3, 3]
+            tr2 = (AS * AS.swapaxes(-1, -2)).sum((-1, -2))  # tr(AΣAΣ)
+            quad = ((cov @ Am[..., None])[..., 0] * Am).sum(-1)
+            out[name] = (mu + tr1, 2.0 * tr2 + 4.0 * quad)
+        else:
+            raise ValueError(f"diagnostic must be one of {DIAGNOSTICS}")
+    return out
 
 
 def _predict_cov_padded(gp: GPFit, xg, diag_add: float):

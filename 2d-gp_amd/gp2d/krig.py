@@ -182,6 +182,34 @@ class Krig:
         shp = [np.size(y), -1]
         return {name: (mu.reshape(shp), var.reshape(shp)) for name, (mu, var) in self.predict_fields(pts).items()}
 
+    def predict_gradient(self, Xg):
+        """The velocity gradient tensor at the points Xg with its joint posterior covariance per
+        point: (mean (M, 4), cov (M, 4, 4)) numpy arrays, components engine.GRADIENT_COMPONENTS =
+        (∂f1/∂x1, ∂f1/∂x2, ∂f2/∂x1, ∂f2/∂x2) — (∂u/∂x, ∂u/∂y, ∂v/∂x, ∂v/∂y) for points (x, y) and
+        obs [u; v]; predict_fields' caveat for (Y, X) points stands (engine.predict_gradient)."""
+        self._check()
+        mu, cov = E.predict_gradient(self.gp, Xg, chunk=self.chunk)
+        return _to_numpy(mu), _to_numpy(cov)
+
+    def predict_diagnostics(self, Xg, names=E.DIAGNOSTICS):
+        """Kinematic diagnostics of the fitted flow at the points Xg, each with its variance:
+        {name: (mean, var)} numpy arrays of shape (M,), names from engine.DIAGNOSTICS — divergence,
+        vorticity, normal_strain ∂u/∂x − ∂v/∂y, shear_strain ∂v/∂x + ∂u/∂y, and okubo_weiss
+        σ_n² + σ_s² − ζ² with its Gaussian moments (engine.flow_diagnostics of one
+        predict_gradient).  Replaces the finite differences of a predicted grid: exact, with error
+        bars that account for the covariance between the derivatives, on any set of points."""
+        self._check()
+        mu, cov = E.predict_gradient(self.gp, Xg, chunk=self.chunk)
+        return {name: (_to_numpy(a), _to_numpy(v)) for name, (a, v) in E.flow_diagnostics(mu, cov, names).items()}
+
+    def predict_diagnostics_grid(self, x, y):
+        """predict_diagnostics on the grid meshgrid(x, y) of predict_grid (points (x, y), components
+        (u, v)): {name: (mean, var)}, each reshaped to [y.size, x.size]."""
+        X, Y = np.meshgrid(x, y)
+        pts = np.stack([X.reshape(-1), Y.reshape(-1)], 1)
+        shp = [np.size(y), -1]
+        return {name: (mu.reshape(shp), var.reshape(shp)) for name, (mu, var) in self.predict_diagnostics(pts).items()}
+
     # ------------------------------------------------------------------ joint covariance, samples
     def predict_cov(self, Xg):
         """(mean (2M, 1), cov (2M, 2M)) numpy arrays: the posterior mean and the full latent

@@ -212,6 +212,42 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
                        int compute_var, double* mean, double* var, int64_t chunk,
                        void* work, size_t work_bytes, void* stream);
 
+/* ---- predict: the velocity gradient tensor with its 4 × 4 posterior covariance ----------
+ * ∇f = (g0, g1, g2, g3) = (∂f1/∂x1, ∂f1/∂x2, ∂f2/∂x1, ∂f2/∂x2) at m points, component c = 2a + b
+ * (a: field component, b: direction), with the joint posterior covariance of the four per point,
+ * from the fit of the velocity observations (W, alpha as for gp2d_predict; points (x1, x2) and
+ * components (f1, f2) as for gp2d_predict_field, whose (Y, X) caveat stands).  Every linear
+ * kinematic diagnostic is aᵀ∇f with variance aᵀΣa — divergence g0 + g3, vorticity g2 − g1, normal
+ * strain g0 − g3, shear strain g2 + g1 — and the Okubo–Weiss parameter σ_n² + σ_s² − ζ² is a
+ * quadratic form whose Gaussian moments need exactly this Σ.  Replaces the finite differences
+ * the reference's users take of its predicted grids (GP_plots.py), which have no error bar, work
+ * on grids only and carry a truncation error on the kernel's own scale; separate per-field
+ * predicts cannot give the covariance between fields.
+ * The cross-covariances are third derivatives of the SE potentials (csrc/grad.hpp, DESIGN.md
+ * §3.8).  Kernels: VECTOR2D and VECTOR_ST of kind DIVFREE, CURLFREE or MIXED; KIND_SCALAR and the
+ * ARD family are refused.
+ * gp2d_grad_prior_cov: the 4 × 4 prior covariance of ∇f at one point, row-major, symmetric:
+ *   cov(∂_b f_a, ∂_d f_c) = w_cf/ℓ_cf⁴·S_acbd + w_df/ℓ_df⁴·(4 δ_ac δ_bd − S_acbd) (× var_t for
+ *   VECTOR_ST), S_pqbd = δ_pq δ_bd + δ_pb δ_qd + δ_pd δ_qb; singular along the divergence for
+ *   DIVFREE and along the vorticity for CURLFREE.  Host only; < 0 and NaNs on bad input.
+ * gp2d_predict_grad: mean[4·j + c] (4m doubles) and, if compute_cov, cov[16·j + 4a + b] =
+ *   prior_ab − Σ_i V_ia·V_ib with V = W·C, C the cross-covariance of the observations with target
+ *   j's four components (16m doubles; exactly symmetric: (a, b) and (b, a) are stored from one
+ *   value; no noise or clipping mode: a gradient is never observed).  compute_cov = 0 leaves cov
+ *   untouched.  chunk: a positive multiple of 64; workspace gp2d_predict_grad_workspace(n, chunk)
+ *   = 8·chunk·(4n + 14·(n/128 + 1)) bytes: C (n × 4·chunk) | the mean's partial sums | ten Gram
+ *   partial sums per target and 128-row block.  gp2d_predict's loop; the product is its GEMM on
+ *   4·chunk columns with the Gram of each target's four columns formed in the epilogue from the
+ *   accumulators (V is never stored).  Deterministic in the same way: no atomics, fixed reduction
+ *   order, results do not depend on the sharding of the targets.                             */
+int gp2d_grad_prior_cov(const gp2d_kernel_t* k, double out[16]);
+size_t gp2d_predict_grad_workspace(int64_t n, int64_t chunk);
+int gp2d_predict_grad(const double* W, int64_t n, int64_t ldw, const double* alpha,
+                      const double* xtr, int64_t ntr, int64_t ntr_pad,
+                      const double* xg, int64_t m, const gp2d_kernel_t* k,
+                      int compute_cov, double* mean, double* cov, int64_t chunk,
+                      void* work, size_t work_bytes, void* stream);
+
 /* ---- predict: joint posterior covariance of the velocity at the target points -------
  * The reference forms the full matrix
  *   Kss = compute_K(Xs, Ys, …);  Cov = Kss − np.dot(Ks, np.dot(Ki, Ks.T))   (GP_laser.py:128-129)
