@@ -19,6 +19,7 @@
 #include "ozaki_host.hpp"
 #include "factor_host.hpp"
 #include "lml.hpp"
+#include "lml_host.hpp"
 #include "dfact.hpp"
 #include "order.hpp"
 #include "../../include/gp2d.h"
@@ -984,15 +985,14 @@ int gp2d_zero_upper(double* A, int64_t n, int64_t lda, void* stream) {
 }
 
 // ------------------------------------------------------------------------ POTRS
-size_t gp2d_potrs_workspace(int64_t n) { return (size_t)n * sizeof(double) * (1 + (size_t)(n / NB + 1)); }
+size_t gp2d_potrs_workspace(int64_t n) { return PotrsWork(n).total; }
 
 int gp2d_potrs_inv(const double* W, int64_t n, int64_t ldw, const double* y, double* alpha, void* work,
                    size_t work_bytes, void* stream) {
   GP2D_REQUIRE(n % NB == 0 && n > 0, "potrs: n must be a positive multiple of 128");
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_potrs_workspace(n), "potrs: workspace too small");
   hipStream_t s = S(stream);
-  double* z = reinterpret_cast<double*>(work);
-  double* part = z + n;
+  const auto [z, part] = PotrsWork(n).at(work);
   trmv_n_lower_kernel<<<(unsigned)((n + 3) / 4), 256, 0, s>>>(W, n, ldw, y, z);
   GP2D_CHECK(check_launch("trmv_n_lower_kernel"));
   const int64_t nseg = n / NB;
@@ -1787,18 +1787,32 @@ SlotMap grad_slots(const gp2d_kernel_t* k, bool with_noise) {
   }
   return m;
 }
+
+// A pair gradient (lml.hpp): weights ⊙ ∂K/∂θ summed over the pairs of the na row points xa and the
+// nb column points xb (ncols_pad: nb padded to whole tiles) into `partial`, then out[g] = scale ·
+// the blocks' sum of output g's slot.
+template <class Weights>
+int launch_pair_grad(const gp2d_kernel_t* k, const double* xa, int64_t na, const double* xb, int64_t nb,
+                     int64_t ncols_pad, const Weights& weights, double* partial, double scale, bool with_noise,
+                     double* out, hipStream_t s) {
+  const dim3 grid((unsigned)(ncols_pad / PT_TILE), (unsigned)((na + LML_ROWS - 1) / LML_ROWS));
+  if (is_vector_family(k)) {
+    const VecFamily fam{{make_vec_params(k), k->l_df, k->l_cf, k->ls[0][0]}};
+    pair_grad_kernel<<<grid, 256, 0, s>>>(xa, na, xb, nb, fam, weights, partial);
+  } else {
+    const ArdFamily fam{make_ard_params(k)};
+    pair_grad_kernel<<<grid, 256, 0, s>>>(xa, na, xb, nb, fam, weights, partial);
+  }
+  GP2D_CHECK(check_launch("pair_grad_kernel"));
+  const SlotMap sm = grad_slots(k, with_noise);
+  grad_sum_kernel<<<sm.ng, 256, 0, s>>>(partial, grad_blocks(ncols_pad, na), sm, scale, out);
+  return check_launch("grad_sum_kernel");
+}
 }  // namespace
 
 extern "C" {
 
-static int64_t grad_blocks(int64_t ncols_pad, int64_t nrows) {
-  return (ncols_pad / PT_TILE) * ((nrows + LML_ROWS - 1) / LML_ROWS);
-}
-
-size_t gp2d_lml_grad_workspace(int64_t n) {
-  const int64_t nblk = (n / PT_TILE + 1) * (n / LML_ROWS + 1);
-  return sizeof(double) * (2 * (size_t)n * (size_t)n + (size_t)nblk * LML_MAXG);
-}
+size_t gp2d_lml_grad_workspace(int64_t n) { return LmlGradWork(n).total; }
 
 int gp2d_lml_grad(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
                   int64_t ntr_pad, const gp2d_kernel_t* k, double* grad_dev, void* work, size_t work_bytes,
@@ -1811,36 +1825,22 @@ int gp2d_lml_grad(const double* W, int64_t n, int64_t ldw, const double* alpha, 
   GP2D_REQUIRE(ntr >= 1 && ntr <= ntr_pad && ldw >= n, "lml_grad: bad sizes");
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_lml_grad_workspace(n), "lml_grad: workspace too small");
   hipStream_t s = S(stream);
-  double* V = reinterpret_cast<double*>(work);
-  double* C = V + (size_t)n * n;
-  double* partial = C + (size_t)n * n;
+  const auto [Wt, C, partial] = LmlGradWork(n).at(work);
   // Wt = Wᵀ (upper), C = Wt·W = K_y⁻¹, lower tiles only
-  transpose_kernel<<<dim3((unsigned)(n / 64), (unsigned)(n / 64)), 256, 0, s>>>(W, n, ldw, V);
+  transpose_kernel<<<dim3((unsigned)(n / 64), (unsigned)(n / 64)), 256, 0, s>>>(W, n, ldw, Wt);
   GP2D_CHECK(check_launch("transpose_kernel"));
   GemmParams p = gemm_params();
-  p.A = V; p.lda = n;
+  p.A = Wt; p.lda = n;
   p.B = W; p.ldb = ldw;
   p.C = C; p.ldc = n;
   p.M = (int)n; p.N = (int)n; p.K = (int)n;
   p.a_upper = 1; p.c_lower = 1;
   GP2D_CHECK((launch_gemm<false, EPI_STORE>(p, 1, s)));
-  const dim3 grid((unsigned)(ntr_pad / PT_TILE), (unsigned)((ntr + LML_ROWS - 1) / LML_ROWS));
-  if (is_vector_family(k)) {
-    VecGradParams gp{make_vec_params(k), k->l_df, k->l_cf, k->ls[0][0]};
-    lml_grad_vec_kernel<<<grid, 256, 0, s>>>(C, n, alpha, xtr, ntr, ntr_pad, gp, partial);
-    GP2D_CHECK(check_launch("lml_grad_vec_kernel"));
-  } else {
-    lml_grad_ard_kernel<<<grid, 256, 0, s>>>(C, n, alpha, xtr, ntr, make_ard_params(k), partial);
-    GP2D_CHECK(check_launch("lml_grad_ard_kernel"));
-  }
-  const SlotMap sm = grad_slots(k, true);
-  grad_sum_kernel<<<sm.ng, 256, 0, s>>>(partial, grad_blocks(ntr_pad, ntr), sm, 0.5, grad_dev);
-  return check_launch("grad_sum_kernel");
+  return launch_pair_grad(k, xtr, ntr, xtr, ntr, ntr_pad, TraceWeights{C, n, alpha, ntr_pad}, partial, 0.5, true,
+                          grad_dev, s);
 }
 
-size_t gp2d_kernel_grad_workspace(int64_t na, int64_t nb) {
-  return sizeof(double) * (size_t)grad_blocks(round_up(nb < 1 ? 1 : nb, PT_TILE), na < 1 ? 1 : na) * LML_MAXG;
-}
+size_t gp2d_kernel_grad_workspace(int64_t na, int64_t nb) { return KernelGradWork(na, nb).total; }
 
 int gp2d_kernel_grad(const double* xa, int64_t na, const double* xb, int64_t nb, const gp2d_kernel_t* k,
                      const double* dL_dK, int64_t ld, double* grad_dev, void* work, size_t work_bytes,
@@ -1851,21 +1851,8 @@ int gp2d_kernel_grad(const double* xa, int64_t na, const double* xb, int64_t nb,
   const int bd = gp2d_block_dim(k);
   GP2D_REQUIRE(ld >= bd * nb, "kernel_grad: ld too small");
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_kernel_grad_workspace(na, nb), "kernel_grad: workspace too small");
-  hipStream_t s = S(stream);
-  double* partial = reinterpret_cast<double*>(work);
-  const int64_t nbp = round_up(nb, PT_TILE);
-  const dim3 grid((unsigned)(nbp / PT_TILE), (unsigned)((na + LML_ROWS - 1) / LML_ROWS));
-  if (is_vector_family(k)) {
-    VecGradParams gp{make_vec_params(k), k->l_df, k->l_cf, k->ls[0][0]};
-    kgrad_vec_kernel<<<grid, 256, 0, s>>>(xa, na, xb, nb, gp, dL_dK, ld, partial);
-    GP2D_CHECK(check_launch("kgrad_vec_kernel"));
-  } else {
-    kgrad_ard_kernel<<<grid, 256, 0, s>>>(xa, na, xb, nb, make_ard_params(k), dL_dK, ld, partial);
-    GP2D_CHECK(check_launch("kgrad_ard_kernel"));
-  }
-  const SlotMap sm = grad_slots(k, false);
-  grad_sum_kernel<<<sm.ng, 256, 0, s>>>(partial, grad_blocks(nbp, na), sm, 1.0, grad_dev);
-  return check_launch("grad_sum_kernel");
+  return launch_pair_grad(k, xa, na, xb, nb, round_up(nb, PT_TILE), DenseWeights{dL_dK, ld, na, nb},
+                          KernelGradWork(na, nb).at(work).partial, 1.0, false, grad_dev, S(stream));
 }
 
 // ------------------------------------------------------------------ instrumentation

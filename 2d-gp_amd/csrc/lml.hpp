@@ -15,8 +15,16 @@
 // the 2×2 block ∂K/∂θ on the fly (no n×n derivative matrices are stored) and
 // contracts it with the stored (row ≥ column) entries of ααᵀ − K_y⁻¹:
 //   vu block (np+p, q): every pair, weight 2 (the uv block is its transpose);
-//   uu, vv blocks: pairs p ≥ q, weight 2 off the diagonal, 1 on it.  Per-block partial sums are reduced in a fixed order, so the
-// result is deterministic.
+//   uu, vv blocks: pairs p ≥ q, weight 2 off the diagonal, 1 on it.
+// GPy's update_gradients_full is the same sum over pairs with a dense caller-supplied dL/dK as
+// the weights.  Both run on one kernel, pair_grad_kernel<Family, Weights>, which owns the thread
+// mapping, the bounds tests, the accumulators, the block reduction and the partial's address; its
+// two axes are policy structs passed by value:
+//   Family   VecFamily (6 slots, three weights per pair) or ArdFamily (9 slots, one weight);
+//   Weights  TraceWeights (the stored triangle above; the diagonal also feeds the noise slot) or
+//            DenseWeights (dL/dK).
+// Per-block partial sums are reduced in a fixed order (grad_sum_kernel), so the result is
+// deterministic.  Workspace layouts: lml_host.hpp.
 //
 // The reference's own gradient (myKernel.update_gradients_full, myKernel.py:59-105)
 // is not a derivative of its kernel (the (2ℓ²−Cℓ²)/ℓ⁵ term has the wrong sign and
@@ -206,129 +214,129 @@ __device__ __forceinline__ void ard_grad_accum(const ArdParams& ap, const double
   }
 }
 
-__device__ __forceinline__ void load_point(const double* x, int64_t i, int dim, double* a) {
-#pragma unroll
-  for (int d = 0; d < 3; ++d) a[d] = (d < dim) ? x[i * dim + d] : 0.0;
-}
+// ---- The pair kernel's two policy axes: which kernel family is differentiated, and where a pair's
+// weights come from.
 
-// Vector family: partial[block][slots 0..3] = Σ over the block's pairs of
-// (ααᵀ − K_y⁻¹) ⊙ ∂K/∂(ℓ_df, ℓ_cf, ratio) and the noise term Σ_diag (α_a² − K_y⁻¹_aa).
-// Grid (ntr_pad/64, ceil(ntr/16)); C = K_y⁻¹, lower triangle, n × n.
-__global__ __launch_bounds__(256) void lml_grad_vec_kernel(const double* __restrict__ C, int64_t n,
-                                                           const double* __restrict__ alpha,
-                                                           const double* __restrict__ x, int64_t ntr, int64_t np,
-                                                           VecGradParams gp, double* __restrict__ partial) {
-  __shared__ double red[6][256];
-  const int64_t q = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
-  const int ty = threadIdx.x >> 6;
-  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (q < ntr) {
-    double b0, b1, b2;
-    vec_point(gp.p, x, q, b0, b1, b2);
-    const double aqu = alpha[q], aqv = alpha[np + q];
-#pragma unroll 1
-    for (int r = 0; r < LML_ROWS / 4; ++r) {
-      const int64_t p = (int64_t)blockIdx.y * LML_ROWS + ty + 4 * r;
-      if (p >= ntr) break;
-      const double apu = alpha[p], apv = alpha[np + p];
-      const double* cu = C + p * n;          // row p (u)
-      const double* cv = C + (np + p) * n;   // row np+p (v)
-      // vu entry (np+p, q): always in the stored triangle; weight 2 (uv is its transpose)
-      const double mvu = apv * aqu - cv[q];
-      double w11 = 0.0, w22 = 0.0;
-      if (p >= q) {
-        const double wt = (p == q) ? 1.0 : 2.0;
-        w11 = wt * (apu * aqu - cu[q]);
-        w22 = wt * (apv * aqv - cv[np + q]);
-        if (p == q) acc[3] += w11 + w22;
-      }
-      double a0, a1, a2;
-      vec_point(gp.p, x, p, a0, a1, a2);
-      vec_grad_accum(gp, a0 - b0, a1 - b1, a2 - b2, w11, 2.0 * mvu, w22, acc);
-    }
+struct Point3 { double c[3]; };
+struct VecWeight { double w11, w12, w22; };   // of a pair's k11, k12 (uv and vu together), k22
+
+// Vector families (2-D and spatio-temporal product): slots 0..5, three weights per pair.
+struct VecFamily {
+  static constexpr int NSLOT = 6, NOISE = 3;
+  using Weight = VecWeight;
+  VecGradParams gp;
+  __device__ __forceinline__ Point3 point(const double* __restrict__ x, int64_t i) const {
+    Point3 a;
+    vec_point(gp.p, x, i, a.c[0], a.c[1], a.c[2]);
+    return a;
   }
-  block_reduce_vec<6>(acc, red, partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * LML_MAXG);
-}
-
-// ARD family (slots t·4 + {0: var, 1+d: ls_d}, 8: noise); pairs p ≥ q of the stored triangle.
-__global__ __launch_bounds__(256) void lml_grad_ard_kernel(const double* __restrict__ C, int64_t n,
-                                                           const double* __restrict__ alpha,
-                                                           const double* __restrict__ x, int64_t ntr, ArdParams ap,
-                                                           double* __restrict__ partial) {
-  __shared__ double red[LML_MAXG][256];
-  const int64_t q = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
-  const int ty = threadIdx.x >> 6;
-  double acc[LML_MAXG];
-#pragma unroll
-  for (int a = 0; a < LML_MAXG; ++a) acc[a] = 0.0;
-  if (q < ntr) {
-    double b[3], a[3];
-    load_point(x, q, ap.dim, b);
-    const double aq = alpha[q];
-#pragma unroll 1
-    for (int r = 0; r < LML_ROWS / 4; ++r) {
-      const int64_t p = (int64_t)blockIdx.y * LML_ROWS + ty + 4 * r;
-      if (p >= ntr) break;
-      if (p < q) continue;
-      const double wt = ((p == q) ? 1.0 : 2.0) * (alpha[p] * aq - C[p * n + q]);
-      load_point(x, p, ap.dim, a);
-      ard_grad_accum(ap, a, b, wt, acc);
-      if (p == q) acc[8] += wt;
-    }
+  __device__ __forceinline__ void accum(const Point3& a, const Point3& b, const Weight& w, double* acc) const {
+    vec_grad_accum(gp, a.c[0] - b.c[0], a.c[1] - b.c[1], a.c[2] - b.c[2], w.w11, w.w12, w.w22, acc);
   }
-  block_reduce_vec<LML_MAXG>(acc, red, partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * LML_MAXG);
-}
+};
 
-// GPy Kern.update_gradients_full (myKernel.py:59-105, exact derivative): Σ_ab G_ab ∂K_ab/∂θ for a
-// caller-supplied G = dL/dK, (bd·na) × (bd·nb) component-major without padding, leading dim ld.
-// Grid (ceil(nb/64), ceil(na/16)).
-__global__ __launch_bounds__(256) void kgrad_vec_kernel(const double* __restrict__ xa, int64_t na,
-                                                        const double* __restrict__ xb, int64_t nb, VecGradParams gp,
-                                                        const double* __restrict__ G, int64_t ld,
-                                                        double* __restrict__ partial) {
-  __shared__ double red[6][256];
+// ARD family: slots t·4 + {0: var, 1+d: ls_d} and 8, one weight per pair.
+struct ArdFamily {
+  static constexpr int NSLOT = LML_MAXG, NOISE = 8;
+  using Weight = double;
+  ArdParams ap;
+  __device__ __forceinline__ Point3 point(const double* __restrict__ x, int64_t i) const {
+    Point3 a;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) a.c[d] = (d < ap.dim) ? x[i * ap.dim + d] : 0.0;
+    return a;
+  }
+  __device__ __forceinline__ void accum(const Point3& a, const Point3& b, Weight w, double* acc) const {
+    ard_grad_accum(ap, a.c, b.c, w, acc);
+  }
+};
+
+// A weights source gives column(fam, q), what a thread keeps of its column point q for all its
+// pairs, and pair(fam, p, q, col, w, acc): the weights of pair (p, q), or false for no term.
+
+// The LML gradient's: the stored (row ≥ column) entries of ααᵀ − K_y⁻¹, with C = K_y⁻¹ (n × n, lower
+// triangle) and np the component stride of α and C; the row points are the column points.  An entry
+// off the diagonal stands for its transpose too (weight 2); the diagonal is also ∂K_y/∂noise.
+struct TraceWeights {
+  const double* C;
+  int64_t n;
+  const double* alpha;
+  int64_t np;
+  struct VecCol { double u, v; };
+  __device__ __forceinline__ VecCol column(const VecFamily&, int64_t q) const { return {alpha[q], alpha[np + q]}; }
+  __device__ __forceinline__ double column(const ArdFamily&, int64_t q) const { return alpha[q]; }
+  // vu entry (np+p, q): always in the stored triangle (uv is its transpose); uu, vv: p ≥ q
+  __device__ __forceinline__ bool pair(const VecFamily&, int64_t p, int64_t q, const VecCol& aq, VecWeight& w,
+                                       double* acc) const {
+    const double apu = alpha[p], apv = alpha[np + p];
+    const double* cu = C + p * n;          // row p (u)
+    const double* cv = C + (np + p) * n;   // row np+p (v)
+    const double mvu = apv * aq.u - cv[q];
+    w.w11 = w.w22 = 0.0;
+    if (p >= q) {
+      const double wt = (p == q) ? 1.0 : 2.0;
+      w.w11 = wt * (apu * aq.u - cu[q]);
+      w.w22 = wt * (apv * aq.v - cv[np + q]);
+      if (p == q) acc[VecFamily::NOISE] += w.w11 + w.w22;
+    }
+    w.w12 = 2.0 * mvu;
+    return true;
+  }
+  __device__ __forceinline__ bool pair(const ArdFamily&, int64_t p, int64_t q, double aq, double& w,
+                                       double* acc) const {
+    if (p < q) return false;
+    w = ((p == q) ? 1.0 : 2.0) * (alpha[p] * aq - C[p * n + q]);
+    if (p == q) acc[ArdFamily::NOISE] += w;
+    return true;
+  }
+};
+
+// GPy Kern.update_gradients_full's (myKernel.py:59-105, exact derivative): a caller-supplied
+// G = dL/dK, (bd·na) × (bd·nb) component-major without padding, leading dimension ld.
+struct DenseWeights {
+  const double* G;
+  int64_t ld, na, nb;
+  struct NoCol {};
+  template <class Family>
+  __device__ __forceinline__ NoCol column(const Family&, int64_t) const { return {}; }
+  __device__ __forceinline__ bool pair(const VecFamily&, int64_t p, int64_t q, NoCol, VecWeight& w, double*) const {
+    const double* g0 = G + p * ld;
+    const double* g1 = G + (na + p) * ld;
+    w = {g0[q], g0[nb + q] + g1[q], g1[nb + q]};
+    return true;
+  }
+  __device__ __forceinline__ bool pair(const ArdFamily&, int64_t p, int64_t q, NoCol, double& w, double*) const {
+    w = G[p * ld + q];
+    return true;
+  }
+};
+
+// partial[block][slot] = Σ over the block's pairs (p of the na row points xa, q of the nb column
+// points xb) of weights ⊙ ∂K_pq/∂θ_slot.  Grid (column tiles of 64 points, row blocks of LML_ROWS):
+// a thread keeps one column point and walks LML_ROWS / 4 row points.
+template <class Family, class Weights>
+__global__ __launch_bounds__(256) void pair_grad_kernel(const double* __restrict__ xa, int64_t na,
+                                                        const double* __restrict__ xb, int64_t nb, Family fam,
+                                                        Weights weights, double* __restrict__ partial) {
+  __shared__ double red[Family::NSLOT][256];
   const int64_t q = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
   const int ty = threadIdx.x >> 6;
-  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double acc[Family::NSLOT];
+#pragma unroll
+  for (int a = 0; a < Family::NSLOT; ++a) acc[a] = 0.0;
   if (q < nb) {
-    double b0, b1, b2;
-    vec_point(gp.p, xb, q, b0, b1, b2);
+    const Point3 b = fam.point(xb, q);
+    const auto col = weights.column(fam, q);
 #pragma unroll 1
     for (int r = 0; r < LML_ROWS / 4; ++r) {
       const int64_t p = (int64_t)blockIdx.y * LML_ROWS + ty + 4 * r;
       if (p >= na) break;
-      const double* g0 = G + p * ld;
-      const double* g1 = G + (na + p) * ld;
-      double a0, a1, a2;
-      vec_point(gp.p, xa, p, a0, a1, a2);
-      vec_grad_accum(gp, a0 - b0, a1 - b1, a2 - b2, g0[q], g0[nb + q] + g1[q], g1[nb + q], acc);
+      typename Family::Weight w;
+      if (!weights.pair(fam, p, q, col, w, acc)) continue;
+      fam.accum(fam.point(xa, p), b, w, acc);
     }
   }
-  block_reduce_vec<6>(acc, red, partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * LML_MAXG);
-}
-
-__global__ __launch_bounds__(256) void kgrad_ard_kernel(const double* __restrict__ xa, int64_t na,
-                                                        const double* __restrict__ xb, int64_t nb, ArdParams ap,
-                                                        const double* __restrict__ G, int64_t ld,
-                                                        double* __restrict__ partial) {
-  __shared__ double red[LML_MAXG][256];
-  const int64_t q = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
-  const int ty = threadIdx.x >> 6;
-  double acc[LML_MAXG];
-#pragma unroll
-  for (int a = 0; a < LML_MAXG; ++a) acc[a] = 0.0;
-  if (q < nb) {
-    double b[3], a[3];
-    load_point(xb, q, ap.dim, b);
-#pragma unroll 1
-    for (int r = 0; r < LML_ROWS / 4; ++r) {
-      const int64_t p = (int64_t)blockIdx.y * LML_ROWS + ty + 4 * r;
-      if (p >= na) break;
-      load_point(xa, p, ap.dim, a);
-      ard_grad_accum(ap, a, b, G[p * ld + q], acc);
-    }
-  }
-  block_reduce_vec<LML_MAXG>(acc, red, partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * LML_MAXG);
+  block_reduce_vec<Family::NSLOT>(acc, red, partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * LML_MAXG);
 }
 
 // out[g] = scale · Σ_blocks partial[block][slot[g]], fixed order (one 256-thread block per entry).

@@ -1575,7 +1575,7 @@ def lml_device(gp: GPFit, eval_gradient: bool = False):
     s = _stream_handle(gp.device)
     bd = gp.kernel.block_dim
     out = torch.empty(1, dtype=torch.float64, device=gp.device)
-    N.check(L.gp2d_lml(_ptr(gp.W), gp.n, gp.n, _ptr(gp.alpha), _ptr(gp.y), bd * gp.n_train, _ptr(out), s),
+    N.check(L.gp2d_lml(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.y), bd * gp.n_train, _ptr(out), s),
             "gp2d_lml")
     if not eval_gradient:
         return out, None
@@ -1584,7 +1584,7 @@ def lml_device(gp: GPFit, eval_gradient: bool = False):
     wbytes = int(L.gp2d_lml_grad_workspace(gp.n))
     work = _workspace(wbytes, gp.device)
     g = torch.empty(ng, dtype=torch.float64, device=gp.device)
-    N.check(L.gp2d_lml_grad(_ptr(gp.W), gp.n, gp.n, _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
+    N.check(L.gp2d_lml_grad(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
                             ctypes.byref(desc), _ptr(g), _ptr(work), wbytes, s), "gp2d_lml_grad")
     return out, g
 

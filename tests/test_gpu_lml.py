@@ -154,6 +154,98 @@ def test_kernel_grad_ard_dense():
     assert rel(g, ref) < 1e-12
 
 
+def _kernel_grad_stencil(kind, kw, xa, xb, G):
+    """Σ G ⊙ ∂K/∂(l_df, l_cf, ratio) by test_kernel_grad_dense's 4-point stencil on the oracle's kernel."""
+    ref = np.zeros(3)
+    for i, name in enumerate(("l_df", "l_cf", "ratio")):
+        h = 1e-4 * (kw[name] if name != "ratio" else 1.0)
+        Ks = []
+        for t in (-2, -1, 1, 2):
+            k2 = dict(kw)
+            k2[name] += t * h
+            Ks.append(O.vector_kernel(xa, xb, kind=kind, **k2))
+        ref[i] = np.sum(G * (Ks[0] - 8 * Ks[1] + 8 * Ks[2] - Ks[3]) / (12 * h))
+    return ref
+
+
+# The pair kernel's block is 16 row points × 64 column points: sizes on a block edge and one point
+# past it, for every family × weights source, at the tolerances of the neighbouring sizes' tests.
+_LML_EDGE_CASES = [("vector", kind, ratio, n) for n in (16, 17, 64, 65)
+                   for kind, ratio in (("df", 1.0), ("cf", 0.0), ("mixed", 0.35), ("scalar", 1.0))]
+_LML_EDGE_CASES += [("ard", "T2", 0.0, 64), ("ard", "T2", 0.0, 65), ("vector_st", "mixed", 0.35, 65)]
+
+
+@pytest.mark.parametrize("family,kind,ratio,n", _LML_EDGE_CASES)
+def test_lml_grad_tile_edges(golden, family, kind, ratio, n):
+    if family == "vector":      # test_lml_vs_oracle's data, parameters and tolerances
+        x, y = tracks(n, seed=n)
+        kw = dict(l_df=4.5, l_cf=6.5, ratio=ratio)
+        gp = E.fit(E.KernelSpec(kind=kind, **kw), x, y, 0.01)
+        oval, ograd = O.vector_lml(x, y, kind=kind, noise=0.01, eval_gradient=True, **kw)
+        vtol, gtol = 1e-10 * max(abs(oval), 1.0), 1e-6
+    elif family == "ard":       # test_lml_ard_sklearn's T = 2 model on the fixture's first n points
+        g = golden("lml_sklearn_ard_N128.npz")
+        HP = [float(v) for v in g["T2_HP"]]
+        var, ls = [HP[0], HP[4]], [tuple(HP[1:4]), tuple(HP[5:8])]
+        X, u = g["X"][:n], g["u"][:n]
+        gp = E.fit(E.KernelSpec(family="ard", variances=tuple(var), lengthscales=tuple(ls)), X, u, HP[-1], jitter=1e-10)
+        oval, ograd = O.ard_lml(X, u, var, ls, HP[-1], jitter=1e-10, eval_gradient=True)
+        vtol, gtol = 1e-10 * abs(oval), 1e-10
+    else:                       # test_gpu_st.test_st_lml_grad's data, parameters and tolerances
+        rng = np.random.default_rng(12)
+        X = np.stack([rng.uniform(0, 6, n), rng.uniform(0, 45, n), rng.uniform(0, 60, n)], 1)
+        v = np.cos(X[:, 2] / 9) + 0.1 * X[:, 0] + rng.normal(0, 0.05, n)
+        u = np.sin(X[:, 1] / 7) - 0.05 * X[:, 0] + rng.normal(0, 0.05, n)
+        y = np.concatenate([v, u])
+        kw = dict(kind=kind, l_df=5.0, l_cf=4.0, ratio=ratio, var_t=2.0, l_t=1.5)
+        gp = E.fit(E.KernelSpec(family="vector_st", **kw), X, y, 0.01)
+        oval, ograd = O.vector_st_lml(X, y, noise=0.01, eval_gradient=True, **kw)
+        vtol, gtol = 1e-10 * abs(oval), 1e-6
+    val, grad = E.log_marginal_likelihood(gp, eval_gradient=True)
+    print(family, kind, n, "lml err", abs(val - oval), "of", vtol, "grad rel", rel(grad, ograd), "of", gtol)
+    assert abs(val - oval) <= vtol, (val, oval)
+    assert rel(grad, ograd) < gtol, (grad, ograd)
+
+
+@pytest.mark.parametrize("family,na,nb", [("mixed", 1, 1), ("mixed", 16, 64), ("mixed", 17, 65), ("mixed", 65, 17),
+                                          ("ard", 17, 65)])
+def test_kernel_grad_tile_edges(family, na, nb):
+    if family == "ard":
+        return _kernel_grad_edge_ard(na, nb)
+    rng = np.random.default_rng(9 + na)
+    xa = rng.uniform(0, 12, (na, 2))
+    xb = rng.uniform(0, 12, (nb, 2))
+    G = rng.normal(0, 1, (2 * na, 2 * nb))
+    kw = dict(l_df=3.0, l_cf=4.0, ratio=0.35)
+    ks = E.KernelSpec(kind="mixed", **kw)
+    g = E.kernel_grad(ks, xa, G, xb)
+    ref = _kernel_grad_stencil("mixed", kw, xa, xb, G)
+    print("mixed", na, nb, "grad rel", rel(g, ref), "of 1e-7")
+    assert rel(g, ref) < 1e-7, (g, ref)
+    if na == 65:    # xb = None is the row points themselves
+        Gs = rng.normal(0, 1, (2 * na, 2 * na))
+        assert np.array_equal(E.kernel_grad(ks, xa, Gs), E.kernel_grad(ks, xa, Gs, xa))
+
+
+def _kernel_grad_edge_ard(na, nb):
+    """test_kernel_grad_ard_dense's closed form and tolerance."""
+    rng = np.random.default_rng(10)
+    xa = rng.uniform(0, 5, (na, 3))
+    xb = rng.uniform(0, 5, (nb, 3))
+    G = rng.normal(0, 1, (na, nb))
+    var, ls = (0.7, 0.2), ((1.0, 2.0, 3.0), (4.0, 0.5, 1.5))
+    g = E.kernel_grad(E.KernelSpec(family="ard", variances=var, lengthscales=ls), xa, G, xb)
+    ref = []
+    for v, l in zip(var, ls):
+        e = O.ard_rbf_exact(xa, xb, [1.0], [l])
+        ref.append(np.sum(G * e))
+        for d in range(3):
+            D2 = np.square(xa[:, d][:, None] - xb[:, d][None, :])
+            ref.append(np.sum(G * v * e * D2 / l[d] ** 3))
+    print("ard", na, nb, "grad rel", rel(g, ref), "of 1e-12")
+    assert rel(g, ref) < 1e-12
+
+
 def test_kern_update_gradients_full():
     rng = np.random.default_rng(4)
     X = rng.uniform(0, 20, (60, 2))

@@ -418,6 +418,36 @@ def test_predict_workspace_sizes_are_the_recorded_ones():
         assert int(f(*args)) == want, (f.__name__, args)
 
 
+def test_hyper_workspace_sizes_are_the_recorded_ones():
+    """The hyperparameter path's and the solve's exported workspace sizes (host functions, no device
+    needed) against values recorded from the library of commit ac565a4, before the sizes came from
+    the layout structs of csrc/lml_host.hpp: callers allocate by them, so a layout change must not
+    move them.  (The structs' internal consistency — order, no overlap, alignment, and that the LML
+    gradient's partial region holds its launch's blocks — is a static_assert there.)"""
+    from gp2d import _native as N
+    L = N.lib()
+    recorded = [
+        (L.gp2d_lml_grad_workspace, (0,), 72),                      # no rows: one row of partials
+        (L.gp2d_lml_grad_workspace, (128,), 264088),                # 8·(2·128² + 3·9·9)
+        (L.gp2d_lml_grad_workspace, (256,), 1054696),
+        (L.gp2d_lml_grad_workspace, (8192,), 1078506568),
+        (L.gp2d_lml_grad_workspace, (32768,), 17255551048),
+        (L.gp2d_kernel_grad_workspace, (0, 0), 72),                 # an empty set sizes as one point
+        (L.gp2d_kernel_grad_workspace, (1, 1), 72),
+        (L.gp2d_kernel_grad_workspace, (16, 64), 72),               # exactly one block
+        (L.gp2d_kernel_grad_workspace, (17, 65), 288),              # one point past both edges: 2 × 2
+        (L.gp2d_kernel_grad_workspace, (37, 100), 432),
+        (L.gp2d_kernel_grad_workspace, (4096, 4096), 1179648),
+        (L.gp2d_potrs_workspace, (0,), 0),
+        (L.gp2d_potrs_workspace, (128,), 3072),                     # 8·128·(1 + 2)
+        (L.gp2d_potrs_workspace, (256,), 8192),
+        (L.gp2d_potrs_workspace, (8192,), 4325376),
+        (L.gp2d_potrs_workspace, (32768,), 67633152),
+    ]
+    for f, args, want in recorded:
+        assert int(f(*args)) == want, (f.__name__, args)
+
+
 def test_factor_join_mode_is_per_thread_and_restorable():
     """gp2d_factor_join (host state only, no device needed): a negative argument queries, the
     previous mode is returned, and the mode belongs to the calling thread (engine.fit sets and
