@@ -7,15 +7,26 @@
 //   myKernel.{myKernel,nonDivK,nonRotK}.K   myKernel.py:27-53, 159-176, 255-271
 //   sklearn RBF(ARD)+White as built in krig.scikit_prior   krig.py:174-180
 //
-// One thread evaluates one (row point i, column point j) pair and writes its
-// 2×2 block into the four component blocks; a wave covers 64 consecutive
-// column points, so every store is a coalesced 512-byte row segment.  Work is
-// exp-bound VALU; HBM traffic is the 32 B per pair written.
+// Every cross-covariance of the library — these, fields.hpp's and grad.hpp's — is assembled by one
+// kernel, cross_cov_kernel<Entry>: a thread evaluates one (row point i, column point j) pair and
+// stores the pair's block; a wave covers 64 consecutive column points, so every store of the
+// kernels here is a coalesced 512-byte row segment.  Work is exp-bound VALU; HBM traffic is what a
+// pair writes (32 B for the 2×2 block).
 #pragma once
 #include "common.hpp"
 #include "../../include/gp2d.h"
 
 namespace gp2d {
+
+inline bool is_vector_family(const gp2d_kernel_t* k) {
+  return k->family == GP2D_FAMILY_VECTOR2D || k->family == GP2D_FAMILY_VECTOR_ST;
+}
+
+// Prior variance of the spatio-temporal product's temporal factor (Kt.Kdiag, myKernel.py:362-363);
+// 1 for the purely spatial families.
+inline double temporal_var(const gp2d_kernel_t* k) {
+  return (k->family == GP2D_FAMILY_VECTOR_ST) ? k->var[0] : 1.0;
+}
 
 struct VecParams {
   int kind;
@@ -43,7 +54,7 @@ inline VecParams make_vec_params(const gp2d_kernel_t* k) {
   p.cratio = 1.0 - k->ratio;
   p.same_len = (k->l_df == k->l_cf);
   p.pdim = (k->family == GP2D_FAMILY_VECTOR_ST) ? 3 : 2;
-  p.var_t = (p.pdim == 3) ? k->var[0] : 1.0;
+  p.var_t = temporal_var(k);
   p.ilt2 = (p.pdim == 3) ? 1.0 / (k->ls[0][0] * k->ls[0][0]) : 0.0;
   return p;
 }
@@ -132,106 +143,165 @@ __device__ __forceinline__ double ard_value(const ArdParams& p, const double* a,
   return k;
 }
 
-// Block: 64 (column points) × 4 thread rows; each thread does ROWS_PER_THREAD
-// row points so that the column point's coordinates are loaded once.
+// ---- The pair-tile kernel and its entries.
+
+// A point of any family: at most 3 coordinates, the unused ones 0.
+struct Point3 { double c[3]; };
+
+// Point i of a family's point array — in global memory or in the kernel's staged tile.  A vector
+// family's is (t, x1, x2), ARD's its first `dim` coordinates.
+__device__ __forceinline__ Point3 read_point(const VecParams& p, const double* __restrict__ x, int64_t i) {
+  Point3 a;
+  vec_point(p, x, i, a.c[0], a.c[1], a.c[2]);
+  return a;
+}
+__device__ __forceinline__ Point3 read_point(const ArdParams& p, const double* __restrict__ x, int64_t i) {
+  Point3 a;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) a.c[d] = (d < p.dim) ? x[i * p.dim + d] : 0.0;
+  return a;
+}
+__device__ __forceinline__ int point_stride(const VecParams& p) { return p.pdim; }
+__device__ __forceinline__ int point_stride(const ArdParams& p) { return p.dim; }
+
+// Block: 64 (column points) × 4 thread rows; each thread does ASM_ROWS / 4 row points so that the
+// column point's coordinates are loaded once.
 constexpr int ASM_ROWS = 16;
 constexpr int ASM_LOWER = 2;   // `symmetric` mode: K_y's lower triangle only (gp2d_assemble)
 
-// j_off / col_comp (gp2d_assemble_cols): column points start at j_off and only the columns of
-// component col_comp (0: u, 1: v; −1: both) are written — the same per-element arithmetic.
-//
-// The workgroup's 64 column points are staged once through LDS (wave 0 loads the tile with one
-// coalesced 1–1.5 KB read, every wave reads it back); the row point of a wave is wave-uniform
-// (readfirstlane'd index: scalar loads).  symmetric = ASM_LOWER writes only the lower triangle
-// (C ≤ R) of the n × n matrix (n = 2·na_pad, component-major) — all gp2d_potrf uses (its
-// diagonal kernel loads the 32×32 sub-blocks whole but never uses, nor stores, their upper
-// parts; the rest of the upper triangle it zeroes at its end) — i.e. K_uu's and K_vv's lower
-// halves and all of K_vu: half the stores, n(n+1)/2 doubles (GP_scripts.py:80-88 likewise
-// fills one triangle of compute_K and mirrors it).  Row segments wholly above the diagonal are
-// skipped per wave (no kernel evaluation either when all four blocks' segments are).
-__global__ __launch_bounds__(256) void assemble_vec_kernel(
+// out (ROWS·na_pad rows, leading dimension ld) = the cross-covariance of the row points xa with the
+// column points j_off + [0, 64·gridDim.x) of xb.  The kernel owns the walk: the workgroup's 64
+// column points are staged once through LDS (wave 0 loads the tile with one coalesced 0.5–1.5 KB
+// read, every wave reads it back), the row point of a wave is wave-uniform (readfirstlane'd index:
+// scalar loads), a pair with a padded point gets the entry's fixed value instead of an evaluation,
+// and the pair's ROWS × COLS block goes to rows r·na_pad + i, columns entry.col(j, c, nb_pad).
+// An Entry, passed by value, supplies what differs:
+//   ROWS, COLS       the block shape of a pair;
+//   layout()         the family's point layout (read_point, point_stride);
+//   skip(i, jt, na_pad)   true: the row point is skipped whole, before any evaluation;
+//   keep(i, j)       once per row point: which of the block's stores are kept
+//                    (Keep::at(r, c)).  StoresAll: nothing skipped, every store kept;
+//   col(j, c, np)    the column of entry c of column point j;
+//   value(a, b, diag, v), padded(diag, v)   the block of a valid pair and of a padded one; diag
+//                    is i == j.
+// Launch: grid (column points / 64, ⌈na_pad / ASM_ROWS⌉), 256 threads (launch_cross_cov).
+struct KeepAll {
+  __device__ __forceinline__ bool at(int, int) const { return true; }
+};
+struct StoresAll {
+  using Keep = KeepAll;
+  __device__ __forceinline__ bool skip(int64_t, int64_t, int64_t) const { return false; }
+  __device__ __forceinline__ Keep keep(int64_t, int64_t) const { return {}; }
+};
+
+template <class Entry>
+__global__ __launch_bounds__(256) void cross_cov_kernel(
     const double* __restrict__ xa, int64_t na, int64_t na_pad,
     const double* __restrict__ xb, int64_t nb, int64_t nb_pad,
-    VecParams p, double diag_add, int symmetric, double* __restrict__ out, int64_t ld, int64_t j_off = 0,
-    int col_comp = -1) {
+    Entry e, double* __restrict__ out, int64_t ld, int64_t j_off) {
   __shared__ double colpts[3 * 64];
+  const int pdim = point_stride(e.layout());
+  __builtin_assume(j_off >= 0);   // column points count from 0: col()'s j / 16, j % 16 are shifts (grad_col)
   const int64_t jt = j_off + (int64_t)blockIdx.x * 64;   // the tile's first column point
   const int lane = threadIdx.x & 63;
   const int ty = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t j = jt + lane;
   const bool jv = j < nb;
-  const bool lower = symmetric == ASM_LOWER;
   if (ty == 0) {
-    for (int e = lane; e < p.pdim * 64; e += 64) {   // the tile's points, coalesced
-      const int64_t g = jt * p.pdim + e;
-      colpts[e] = (g < nb * p.pdim) ? xb[g] : 0.0;
+    for (int t = lane; t < pdim * 64; t += 64) {   // the tile's points, coalesced
+      const int64_t g = jt * pdim + t;
+      colpts[t] = (g < nb * pdim) ? xb[g] : 0.0;
     }
   }
   __syncthreads();
-  double b0 = 0.0, b1 = 0.0, b2 = 0.0;
-  if (p.pdim == 3) {
-    b0 = colpts[3 * lane]; b1 = colpts[3 * lane + 1]; b2 = colpts[3 * lane + 2];
-  } else {
-    b1 = colpts[2 * lane]; b2 = colpts[2 * lane + 1];
-  }
-  // lower mode: matrix column C is kept in matrix row R iff C ≤ R; the wave's segments start at
-  // column cu (u component) and cv (v component)
-  const int64_t cu = jt, cv = nb_pad + jt;
+  const Point3 b = read_point(e.layout(), colpts, lane);
 #pragma unroll 1
   for (int q = 0; q < ASM_ROWS / 4; ++q) {
     const int64_t i = (int64_t)blockIdx.y * ASM_ROWS + ty + 4 * q;   // wave-uniform
     if (i >= na_pad) break;
-    const int64_t R0 = i, R1 = na_pad + i;   // the pair's rows in the u and v components
-    if (lower && cu > R1) continue;          // every segment of this row pair is above the diagonal
-    const bool w_uu = !lower || cu + lane <= R0, w_uv = !lower || cv + lane <= R0;
-    const bool w_vu = !lower || cu + lane <= R1, w_vv = !lower || cv + lane <= R1;
-    double k11, k12, k22;
+    if (e.skip(i, jt, na_pad)) continue;
+    const typename Entry::Keep keep = e.keep(i, j);
+    double v[Entry::ROWS][Entry::COLS];
     if (jv && i < na) {
-      double a0, a1, a2;
-      vec_point(p, xa, i, a0, a1, a2);
-      vec_block_st(p, a0 - b0, a1 - b1, a2 - b2, k11, k12, k22);
-      if (symmetric && i == j) { k11 += diag_add; k22 += diag_add; }
+      e.value(read_point(e.layout(), xa, i), b, i == j, v);
     } else {
-      const double dd = (symmetric && i == j) ? 1.0 : 0.0;  // padded points: identity rows
-      k11 = dd; k12 = 0.0; k22 = dd;
+      e.padded(i == j, v);
     }
-    double* r0 = out + i * ld;
-    double* r1 = out + (na_pad + i) * ld;
-    if (col_comp != 1) {
-      if (w_uu) r0[j] = k11;
-      if (w_vu) r1[j] = k12;
-    }
-    if (col_comp != 0) {
-      if (w_uv) r0[nb_pad + j] = k12;
-      if (w_vv) r1[nb_pad + j] = k22;
+#pragma unroll
+    for (int c = 0; c < Entry::COLS; ++c) {
+#pragma unroll
+      for (int r = 0; r < Entry::ROWS; ++r)
+        if (keep.at(r, c)) out[(r * na_pad + i) * ld + e.col(j, c, nb_pad)] = v[r][c];
     }
   }
 }
 
-__global__ __launch_bounds__(256) void assemble_ard_kernel(
-    const double* __restrict__ xa, int64_t na, int64_t na_pad,
-    const double* __restrict__ xb, int64_t nb, int64_t nb_pad,
-    ArdParams p, double diag_add, int symmetric, double* __restrict__ out, int64_t ld) {
-  const int64_t j = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
-  const int ty = threadIdx.x >> 6;
-  const bool jv = j < nb;
-  double b[3] = {0.0, 0.0, 0.0};
-  for (int d = 0; d < p.dim; ++d) b[d] = jv ? xb[j * p.dim + d] : 0.0;
-#pragma unroll 1
-  for (int q = 0; q < ASM_ROWS / 4; ++q) {
-    const int64_t i = (int64_t)blockIdx.y * ASM_ROWS + ty + 4 * q;
-    if (i >= na_pad) break;
-    double k;
-    if (jv && i < na) {
-      double a[3] = {0.0, 0.0, 0.0};
-      for (int d = 0; d < p.dim; ++d) a[d] = xa[i * p.dim + d];
-      k = ard_value(p, a, b);
-      if (symmetric && i == j) k += diag_add;
-    } else {
-      k = (symmetric && i == j) ? 1.0 : 0.0;
+// symmetric modes (xa == xb) of the two covariance entries: a valid diagonal pair gets diag_add,
+// a padded one the identity.
+__device__ __forceinline__ double padded_diag(int symmetric, bool diag) { return (symmetric && diag) ? 1.0 : 0.0; }
+
+// The 2×2 block of a vector family into the four component blocks (component-major).
+// symmetric = ASM_LOWER writes only the lower triangle (C ≤ R) of the n × n matrix (n = 2·na_pad)
+// — all gp2d_potrf uses (its diagonal kernel loads the 32×32 sub-blocks whole but never uses, nor
+// stores, their upper parts; the rest of the upper triangle it zeroes at its end) — i.e. K_uu's
+// and K_vv's lower halves and all of K_vu: half the stores, n(n+1)/2 doubles (GP_scripts.py:80-88
+// likewise fills one triangle of compute_K and mirrors it).  Row segments wholly above the diagonal
+// are skipped per wave (no kernel evaluation either when all four blocks' segments are).
+// col_comp (gp2d_assemble_cols): only the columns of component col_comp (0: u, 1: v; −1: both)
+// are written — the same per-element arithmetic.
+// The instantiation sits at the SGPR limit of eight waves per SIMD (96, handed out in blocks of 16;
+// DESIGN.md §3.1), which is why lower mode keeps one flag per row point and not four comparisons.
+struct VecEntry {
+  static constexpr int ROWS = 2, COLS = 2;
+  VecParams p;
+  double diag_add;
+  int symmetric, col_comp;
+  // lower mode has xa == xb, so one padded count np: matrix column c·np + j is kept in matrix row
+  // r·np + i iff it is ≤ the row, i.e. r > c (all of K_vu), or r == c and j ≤ i
+  struct Keep {
+    bool lower, tri;   // tri: j ≤ i
+    int comp;
+    __device__ __forceinline__ bool at(int r, int c) const {
+      return comp != 1 - c && (!lower || (r == c ? tri : r > c));   // comp ∈ {−1, 0, 1}
     }
-    out[i * ld + j] = k;
+  };
+  __device__ __forceinline__ const VecParams& layout() const { return p; }
+  // a row pair whose every segment is above the diagonal is skipped whole
+  __device__ __forceinline__ bool skip(int64_t i, int64_t jt, int64_t na_pad) const {
+    return symmetric == ASM_LOWER && jt > na_pad + i;
   }
-}
+  __device__ __forceinline__ Keep keep(int64_t i, int64_t j) const {
+    return {symmetric == ASM_LOWER, j <= i, col_comp};
+  }
+  __device__ __forceinline__ int64_t col(int64_t j, int c, int64_t nb_pad) const { return c * nb_pad + j; }
+  __device__ __forceinline__ void value(const Point3& a, const Point3& b, bool diag, double (&v)[2][2]) const {
+    double k11, k12, k22;
+    vec_block_st(p, a.c[0] - b.c[0], a.c[1] - b.c[1], a.c[2] - b.c[2], k11, k12, k22);
+    if (symmetric && diag) { k11 += diag_add; k22 += diag_add; }
+    v[0][0] = k11; v[0][1] = k12; v[1][0] = k12; v[1][1] = k22;
+  }
+  __device__ __forceinline__ void padded(bool diag, double (&v)[2][2]) const {
+    const double dd = padded_diag(symmetric, diag);
+    v[0][0] = dd; v[0][1] = 0.0; v[1][0] = 0.0; v[1][1] = dd;
+  }
+};
+
+// One value per pair: sklearn's sum of ARD RBF terms.
+struct ArdEntry : StoresAll {
+  static constexpr int ROWS = 1, COLS = 1;
+  ArdParams p;
+  double diag_add;
+  int symmetric;
+  __device__ __forceinline__ const ArdParams& layout() const { return p; }
+  __device__ __forceinline__ int64_t col(int64_t j, int, int64_t) const { return j; }
+  __device__ __forceinline__ void value(const Point3& a, const Point3& b, bool diag, double (&v)[1][1]) const {
+    // plain arrays: indexed by ard_value's run-time loops, they stay in registers (the Point3s did not)
+    const double pa[3] = {a.c[0], a.c[1], a.c[2]}, pb[3] = {b.c[0], b.c[1], b.c[2]};
+    double k = ard_value(p, pa, pb);
+    if (symmetric && diag) k += diag_add;
+    v[0][0] = k;
+  }
+  __device__ __forceinline__ void padded(bool diag, double (&v)[1][1]) const { v[0][0] = padded_diag(symmetric, diag); }
+};
 
 }  // namespace gp2d

@@ -84,10 +84,6 @@ struct TimedLaunch {
   hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 
-static bool is_vector_family(const gp2d_kernel_t* k) {
-  return k->family == GP2D_FAMILY_VECTOR2D || k->family == GP2D_FAMILY_VECTOR_ST;
-}
-
 // coordinates per point: (x1, x2), (t, x1, x2), or the ARD dimension
 static int point_dim(const gp2d_kernel_t* k) {
   return k->family == GP2D_FAMILY_VECTOR2D ? 2 : (k->family == GP2D_FAMILY_VECTOR_ST ? 3 : k->dim);
@@ -125,6 +121,17 @@ static int validate_ozaki_kernel(const gp2d_kernel_t* k) {
   return 0;
 }
 
+// One cross_cov_kernel launch: `ncols` (a multiple of 64) column points of xb from j_off on, against
+// every row point of xa.
+template <class Entry>
+static int launch_cross_cov(const Entry& e, const double* xa, int64_t na, int64_t na_pad, const double* xb,
+                            int64_t nb, int64_t nb_pad, double* out, int64_t ld, int64_t j_off, int64_t ncols,
+                            hipStream_t s) {
+  const dim3 grid((unsigned)(ncols / 64), (unsigned)((na_pad + ASM_ROWS - 1) / ASM_ROWS));
+  cross_cov_kernel<<<grid, 256, 0, s>>>(xa, na, na_pad, xb, nb, nb_pad, e, out, ld, j_off);
+  return check_launch("cross_cov_kernel");
+}
+
 static int assemble_impl(const double* xa, int64_t na, int64_t na_pad, const double* xb, int64_t nb,
                          int64_t nb_pad, const gp2d_kernel_t* k, double diag_add, int symmetric, double* out,
                          int64_t ld, hipStream_t s) {
@@ -137,17 +144,12 @@ static int assemble_impl(const double* xa, int64_t na, int64_t na_pad, const dou
   GP2D_REQUIRE(symmetric >= 0 && symmetric <= ASM_LOWER, "symmetric must be 0, 1 or 2");
   GP2D_REQUIRE(symmetric != ASM_LOWER || (bd == 2 && xa == xb && na == nb && na_pad == nb_pad),
                "symmetric = 2 (lower block triangle) needs a vector kernel and xa == xb");
-  dim3 grid(nb_pad / 64, (na_pad + ASM_ROWS - 1) / ASM_ROWS);
-  if (bd == 2) {
-    assemble_vec_kernel<<<grid, 256, 0, s>>>(xa, na, na_pad, xb, nb, nb_pad, make_vec_params(k), diag_add,
-                                             symmetric, out, ld);
-  } else {
-    assemble_ard_kernel<<<grid, 256, 0, s>>>(xa, na, na_pad, xb, nb, nb_pad, make_ard_params(k), diag_add,
-                                             symmetric, out, ld);
-  }
-  return check_launch("assemble");
+  if (bd == 2)
+    return launch_cross_cov(VecEntry{make_vec_params(k), diag_add, symmetric, -1}, xa, na, na_pad, xb, nb, nb_pad,
+                            out, ld, 0, nb_pad, s);
+  return launch_cross_cov(ArdEntry{{}, make_ard_params(k), diag_add, symmetric}, xa, na, na_pad, xb, nb, nb_pad,
+                          out, ld, 0, nb_pad, s);
 }
-
 
 
 // ------------------------------------------------------------- Ozaki constants
@@ -191,7 +193,7 @@ static int64_t modinv(int64_t a, int64_t m) {  // a⁻¹ mod m (a, m coprime)
 static double kstar_bound(const gp2d_kernel_t* k) {
   // |K*| entries: div-free and curl-free parts are each bounded by 1/ℓ² (see ozaki.hpp);
   // the temporal factor of the spatio-temporal product is ≤ var_t
-  const double vt = (k->family == GP2D_FAMILY_VECTOR_ST) ? k->var[0] : 1.0;
+  const double vt = temporal_var(k);
   switch (k->kind) {
     case GP2D_KIND_SCALAR: return vt;
     case GP2D_KIND_DIVFREE: return vt / (k->l_df * k->l_df);
@@ -256,7 +258,7 @@ double gp2d_kernel_diag(const gp2d_kernel_t* k) {
     for (int t = 0; t < k->nterms; ++t) s += k->var[t];
     return s;
   }
-  const double vt = (k->family == GP2D_FAMILY_VECTOR_ST) ? k->var[0] : 1.0;  // Kt.Kdiag, myKernel.py:362-363
+  const double vt = temporal_var(k);
   switch (k->kind) {
     case GP2D_KIND_SCALAR: return vt * ((1.0 / k->l_df) * (1.0 / k->l_df) * (k->l_df * k->l_df));
     case GP2D_KIND_DIVFREE: return vt * (1.0 / (k->l_df * k->l_df));
@@ -283,10 +285,8 @@ int gp2d_assemble_cols(const double* x, int64_t n, int64_t n_pad, const gp2d_ker
                "assemble_cols: the column range must be 64-aligned and inside one component");
   if (ncols == 0 || n_pad == 0) return 0;
   const int comp = (int)(c0 / n_pad);
-  dim3 grid((unsigned)(ncols / 64), (unsigned)((n_pad + ASM_ROWS - 1) / ASM_ROWS));
-  assemble_vec_kernel<<<grid, 256, 0, S(stream)>>>(x, n, n_pad, x, n, n_pad, make_vec_params(k), diag_add, 1, out, ld,
-                                                   c0 - (int64_t)comp * n_pad, comp);
-  return check_launch("assemble_cols");
+  return launch_cross_cov(VecEntry{make_vec_params(k), diag_add, 1, comp}, x, n, n_pad, x, n, n_pad, out, ld,
+                          c0 - (int64_t)comp * n_pad, ncols, S(stream));
 }
 
 }  // extern "C"
@@ -1141,7 +1141,7 @@ double gp2d_field_prior_var(const gp2d_kernel_t* k, int field) {
   const double w = field_weight(k, field);
   if (w == 0.0) return 0.0;   // the field vanishes by kind (its length scale may be unset)
   const double l = (field == GP2D_FIELD_VORTICITY) ? k->l_df : k->l_cf;
-  const double vt = (k->family == GP2D_FAMILY_VECTOR_ST) ? k->var[0] : 1.0;
+  const double vt = temporal_var(k);
   const double l2 = l * l;
   return vt * (8.0 * w / (l2 * l2));
 }
@@ -1173,16 +1173,14 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
     }
     return 0;
   }
-  const FieldParams fp = make_field_params(k, field);
+  const FieldEntry fe = make_field_entry(k, field);
   // one component per target: the prior is the field's prior variance, no noise, no clipping; untimed
   ChunkedPredict v;
   v.bd = 1;
   v.prior = gp2d_field_prior_var(k, field);
   v.assemble = [=](const double* xc, int64_t cv, int64_t cp, double* Ks) {
     // cov(observations, field) for the chunk: rows = training components, cols = target points
-    const dim3 grid((unsigned)(cp / 64), (unsigned)((ntr_pad + ASM_ROWS - 1) / ASM_ROWS));
-    assemble_field_kernel<<<grid, 256, 0, s>>>(xtr, ntr, ntr_pad, xc, cv, cp, fp, Ks);
-    return check_launch("assemble_field_kernel");
+    return launch_cross_cov(fe, xtr, ntr, ntr_pad, xc, cv, cp, Ks, cp, 0, cp, s);
   };
   return predict_chunks(v, W, n, ldw, alpha, ntr, xg, point_dim(k), m, compute_var, mean, var, chunk, work, s);
 }
@@ -1216,16 +1214,14 @@ int gp2d_predict_grad(const double* W, int64_t n, int64_t ldw, const double* alp
                "predict_grad: workspace too small");
   if (m <= 0) return 0;
   hipStream_t s = S(stream);
-  const GradParams gp = make_grad_params(k);
+  const GradEntry ge = make_grad_entry(k);
   // four columns per target in grad.hpp's layout; the 4 × 4 prior, no noise, no clipping; untimed
   ChunkedPredict v;
   v.bd = GRAD_NC;
   v.gram = true;
   grad_prior_cov(k, v.prior4.p);
   v.assemble = [=](const double* xc, int64_t cv, int64_t cp, double* C) {
-    const dim3 grid((unsigned)(cp / 64), (unsigned)((ntr_pad + ASM_ROWS - 1) / ASM_ROWS));
-    assemble_grad_kernel<<<grid, 256, 0, s>>>(xtr, ntr, ntr_pad, xc, cv, cp, gp, C);
-    return check_launch("assemble_grad_kernel");
+    return launch_cross_cov(ge, xtr, ntr, ntr_pad, xc, cv, cp, C, GRAD_NC * cp, 0, cp, s);
   };
   const auto [C, pm, G] = PredictGradWork(n, chunk).at(work);
   return predict_chunks(v, W, n, ldw, alpha, ntr, xg, point_dim(k), m, compute_cov, mean, cov, chunk, C, pm, G, s);

@@ -16,7 +16,7 @@
 //   cov(∂_b f_a, ∂_d f_c) = w_cf/ℓ_cf⁴·S_acbd + w_df/ℓ_df⁴·(4 δ_ac δ_bd − S_acbd)   (× var_t).
 //
 // Column layout of the cross-covariance matrix C (n × 4·cp), the contract between
-// assemble_grad_kernel, gemm_f64_kernel's EPI_COLGRAM epilogue and grad_finalize_kernel: target t
+// GradEntry, gemm_f64_kernel's EPI_COLGRAM epilogue and grad_finalize_kernel: target t
 // of the chunk, component c, is column 64·(t / 16) + 16·c + (t mod 16).  The four components of a
 // target are 16 columns apart inside one 64-column group, which is how a lane of the GEMM holds its
 // four column accumulators — all ten products Σ_i V_ia·V_ib of a target are in-lane.
@@ -33,24 +33,11 @@ static_assert(GRAD_NPAIR == EPI_COLGRAM_PAIRS, "the epilogue and the finalize ag
 // column of component c of chunk target t
 __host__ __device__ inline int64_t grad_col(int64_t t, int c) { return 64 * (t / 16) + 16 * c + (t % 16); }
 
-struct GradParams {
-  VecParams v;          // point layout, temporal factor, 1/ℓ² of both parts, same_len
-  double w_df, w_cf;    // weights of the div-free and curl-free parts (0: the part is absent)
-};
-
-inline GradParams make_grad_params(const gp2d_kernel_t* k) {
-  GradParams p;
-  p.v = make_vec_params(k);
-  p.w_df = field_weight(k, GP2D_FIELD_VORTICITY);
-  p.w_cf = field_weight(k, GP2D_FIELD_DIVERGENCE);
-  return p;
-}
-
 // The 4 × 4 prior covariance of ∇f at one point, row-major; a part of weight 0 is left out (its
 // length scale may be unset).
 inline void grad_prior_cov(const gp2d_kernel_t* k, double out[16]) {
   const double w_df = field_weight(k, GP2D_FIELD_VORTICITY), w_cf = field_weight(k, GP2D_FIELD_DIVERGENCE);
-  const double vt = (k->family == GP2D_FAMILY_VECTOR_ST) ? k->var[0] : 1.0;
+  const double vt = temporal_var(k);
   const double q_df = (w_df != 0.0) ? w_df / (k->l_df * k->l_df * k->l_df * k->l_df) : 0.0;
   const double q_cf = (w_cf != 0.0) ? w_cf / (k->l_cf * k->l_cf * k->l_cf * k->l_cf) : 0.0;
   for (int a = 0; a < 2; ++a)
@@ -72,73 +59,53 @@ __device__ __forceinline__ GradPart grad_part(double s, double a, double d1, dou
   return {d1 * (3.0 * a2 - q1), d2 * (a2 - q1), d1 * (a2 - q2), d2 * (3.0 * a2 - q2), hs * d1, hs * d2};
 }
 
-// C = cov(observations, ∇f at the targets): (2·na_pad) × 4·cp with leading dimension 4·cp, columns
-// in the layout above; rows i and na_pad + i hold the f1 and f2 cross-covariances of training point
-// i.  assemble_field_kernel's thread mapping: the workgroup's 64 target points are staged once
-// through LDS, the wave's training point is wave-uniform.  The tile's targets own columns
-// [4·jt, 4·jt + 256); for a fixed component the wave's 64 lanes store four 128-byte runs per row.
-// One exp per pair and part (one for a mixed kernel of equal lengths), one more for the
-// spatio-temporal product.  Every element of the buffer is written — 0.0 for padded training rows
-// and padded targets — since the Gram product reads all of it and the workspace is reused.
-// Launch: grid (cp / 64, ⌈na_pad / ASM_ROWS⌉), 256 threads; cp a multiple of 64.
-__global__ __launch_bounds__(256) void assemble_grad_kernel(
-    const double* __restrict__ xa, int64_t na, int64_t na_pad,
-    const double* __restrict__ xg, int64_t m, int64_t cp, GradParams p, double* __restrict__ out) {
-  __shared__ double colpts[3 * 64];
-  const int pdim = p.v.pdim;
-  const int64_t jt = (int64_t)blockIdx.x * 64;   // the tile's first target point
-  const int lane = threadIdx.x & 63;
-  const int ty = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t j = jt + lane;
-  const bool jv = j < m;
-  if (ty == 0) {
-    for (int e = lane; e < pdim * 64; e += 64) {   // the tile's points, coalesced
-      const int64_t g = jt * pdim + e;
-      colpts[e] = (g < m * pdim) ? xg[g] : 0.0;
-    }
-  }
-  __syncthreads();
-  double b0 = 0.0, b1, b2;
-  if (pdim == 3) {
-    b0 = colpts[3 * lane]; b1 = colpts[3 * lane + 1]; b2 = colpts[3 * lane + 2];
-  } else {
-    b1 = colpts[2 * lane]; b2 = colpts[2 * lane + 1];
-  }
-  const int64_t ld = GRAD_NC * cp;
-  const int64_t col = grad_col(j, 0);   // j < cp: the last column written is < 4·cp
-#pragma unroll 1
-  for (int q = 0; q < ASM_ROWS / 4; ++q) {
-    const int64_t i = (int64_t)blockIdx.y * ASM_ROWS + ty + 4 * q;   // wave-uniform
-    if (i >= na_pad) break;
-    double c1[GRAD_NC] = {0.0, 0.0, 0.0, 0.0}, c2[GRAD_NC] = {0.0, 0.0, 0.0, 0.0};
-    if (jv && i < na) {
-      double a0, a1, a2;
-      vec_point(p.v, xa, i, a0, a1, a2);
-      const double d1 = a1 - b1, d2 = a2 - b2;
-      const double r2 = d1 * d1 + d2 * d2;
-      const double tf = time_factor(p.v, a0 - b0);
-      double e_df = 0.0;
-      if (p.w_df != 0.0) {   // δ_pa·h_b − T_pab
-        e_df = exp(-0.5 * r2 * p.v.il_df2);
-        const GradPart t = grad_part(p.w_df * tf * e_df, p.v.il_df2, d1, d2, r2);
-        c1[0] = t.h1 - t.t111; c1[1] = t.h2 - t.t112; c1[2] = -t.t112; c1[3] = -t.t122;
-        c2[0] = -t.t112; c2[1] = -t.t122; c2[2] = t.h1 - t.t122; c2[3] = t.h2 - t.t222;
-      }
-      if (p.w_cf != 0.0) {   // T_pab
-        const double e = (p.w_df != 0.0 && p.v.same_len) ? e_df : exp(-0.5 * r2 * p.v.il_cf2);
-        const GradPart t = grad_part(p.w_cf * tf * e, p.v.il_cf2, d1, d2, r2);
-        c1[0] += t.t111; c1[1] += t.t112; c1[2] += t.t112; c1[3] += t.t122;
-        c2[0] += t.t112; c2[1] += t.t122; c2[2] += t.t122; c2[3] += t.t222;
-      }
-    }
-    double* r0 = out + i * ld + col;
-    double* r1 = out + (na_pad + i) * ld + col;
+// cross_cov_kernel's entry for C = cov(observations, ∇f at the targets): (2·na_pad) × 4·cp with
+// leading dimension 4·cp, columns in the layout above; rows i and na_pad + i hold the f1 and f2
+// cross-covariances of training point i.  The tile's targets own columns [4·jt, 4·jt + 256); for a
+// fixed component the wave's 64 lanes store four 128-byte runs per row.  One exp per pair and part
+// (one for a mixed kernel of equal lengths), one more for the spatio-temporal product.  Every
+// element of the buffer is written — 0.0 for padded training rows and padded targets — since the
+// Gram product reads all of it and the workspace is reused.
+struct GradEntry : StoresAll {
+  static constexpr int ROWS = 2, COLS = GRAD_NC;
+  VecParams v;          // point layout, temporal factor, 1/ℓ² of both parts, same_len
+  double w_df, w_cf;    // weights of the div-free and curl-free parts (0: the part is absent)
+  __device__ __forceinline__ const VecParams& layout() const { return v; }
+  // j < cp: the last column written is < 4·cp
+  __device__ __forceinline__ int64_t col(int64_t j, int c, int64_t) const { return grad_col(j, c); }
+  __device__ __forceinline__ void padded(bool, double (&o)[2][GRAD_NC]) const {
 #pragma unroll
-    for (int c = 0; c < GRAD_NC; ++c) {
-      r0[16 * c] = c1[c];
-      r1[16 * c] = c2[c];
+    for (int c = 0; c < GRAD_NC; ++c) o[0][c] = o[1][c] = 0.0;
+  }
+  __device__ __forceinline__ void value(const Point3& a, const Point3& b, bool, double (&o)[2][GRAD_NC]) const {
+    padded(false, o);
+    double* c1 = o[0];
+    double* c2 = o[1];
+    const double d1 = a.c[1] - b.c[1], d2 = a.c[2] - b.c[2];
+    const double r2 = d1 * d1 + d2 * d2;
+    const double tf = time_factor(v, a.c[0] - b.c[0]);
+    double e_df = 0.0;
+    if (w_df != 0.0) {   // δ_pa·h_b − T_pab
+      e_df = exp(-0.5 * r2 * v.il_df2);
+      const GradPart t = grad_part(w_df * tf * e_df, v.il_df2, d1, d2, r2);
+      c1[0] = t.h1 - t.t111; c1[1] = t.h2 - t.t112; c1[2] = -t.t112; c1[3] = -t.t122;
+      c2[0] = -t.t112; c2[1] = -t.t122; c2[2] = t.h1 - t.t122; c2[3] = t.h2 - t.t222;
+    }
+    if (w_cf != 0.0) {   // T_pab
+      const double e = (w_df != 0.0 && v.same_len) ? e_df : exp(-0.5 * r2 * v.il_cf2);
+      const GradPart t = grad_part(w_cf * tf * e, v.il_cf2, d1, d2, r2);
+      c1[0] += t.t111; c1[1] += t.t112; c1[2] += t.t112; c1[3] += t.t122;
+      c2[0] += t.t112; c2[1] += t.t122; c2[2] += t.t122; c2[3] += t.t222;
     }
   }
+};
+
+inline GradEntry make_grad_entry(const gp2d_kernel_t* k) {
+  GradEntry p;
+  p.v = make_vec_params(k);
+  p.w_df = field_weight(k, GP2D_FIELD_VORTICITY);
+  p.w_cf = field_weight(k, GP2D_FIELD_DIVERGENCE);
+  return p;
 }
 
 // Per target of the chunk: the mean's partial sums of its four columns and the ten Gram partials

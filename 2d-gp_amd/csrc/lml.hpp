@@ -217,7 +217,6 @@ __device__ __forceinline__ void ard_grad_accum(const ArdParams& ap, const double
 // ---- The pair kernel's two policy axes: which kernel family is differentiated, and where a pair's
 // weights come from.
 
-struct Point3 { double c[3]; };
 struct VecWeight { double w11, w12, w22; };   // of a pair's k11, k12 (uv and vu together), k22
 
 // Vector families (2-D and spatio-temporal product): slots 0..5, three weights per pair.
@@ -225,11 +224,7 @@ struct VecFamily {
   static constexpr int NSLOT = 6, NOISE = 3;
   using Weight = VecWeight;
   VecGradParams gp;
-  __device__ __forceinline__ Point3 point(const double* __restrict__ x, int64_t i) const {
-    Point3 a;
-    vec_point(gp.p, x, i, a.c[0], a.c[1], a.c[2]);
-    return a;
-  }
+  __device__ __forceinline__ const VecParams& layout() const { return gp.p; }
   __device__ __forceinline__ void accum(const Point3& a, const Point3& b, const Weight& w, double* acc) const {
     vec_grad_accum(gp, a.c[0] - b.c[0], a.c[1] - b.c[1], a.c[2] - b.c[2], w.w11, w.w12, w.w22, acc);
   }
@@ -240,12 +235,7 @@ struct ArdFamily {
   static constexpr int NSLOT = LML_MAXG, NOISE = 8;
   using Weight = double;
   ArdParams ap;
-  __device__ __forceinline__ Point3 point(const double* __restrict__ x, int64_t i) const {
-    Point3 a;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) a.c[d] = (d < ap.dim) ? x[i * ap.dim + d] : 0.0;
-    return a;
-  }
+  __device__ __forceinline__ const ArdParams& layout() const { return ap; }
   __device__ __forceinline__ void accum(const Point3& a, const Point3& b, Weight w, double* acc) const {
     ard_grad_accum(ap, a.c, b.c, w, acc);
   }
@@ -325,7 +315,7 @@ __global__ __launch_bounds__(256) void pair_grad_kernel(const double* __restrict
 #pragma unroll
   for (int a = 0; a < Family::NSLOT; ++a) acc[a] = 0.0;
   if (q < nb) {
-    const Point3 b = fam.point(xb, q);
+    const Point3 b = read_point(fam.layout(), xb, q);
     const auto col = weights.column(fam, q);
 #pragma unroll 1
     for (int r = 0; r < LML_ROWS / 4; ++r) {
@@ -333,7 +323,7 @@ __global__ __launch_bounds__(256) void pair_grad_kernel(const double* __restrict
       if (p >= na) break;
       typename Family::Weight w;
       if (!weights.pair(fam, p, q, col, w, acc)) continue;
-      fam.accum(fam.point(xa, p), b, w, acc);
+      fam.accum(read_point(fam.layout(), xa, p), b, w, acc);
     }
   }
   block_reduce_vec<Family::NSLOT>(acc, red, partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * LML_MAXG);

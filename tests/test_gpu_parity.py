@@ -56,6 +56,48 @@ def test_assemble_golden_small(golden):
         assert rel(E.assemble(ks, xb, xa).cpu().numpy(), g[f"Ks_{kind}"]) < 1e-13
 
 
+RAW_KERNELS = {
+    "df": dict(kind="df", l_df=2.5),
+    "mixed_equal": dict(kind="mixed", l_df=3.0, l_cf=3.0, ratio=0.3),
+    "mixed": dict(kind="mixed", l_df=2.5, l_cf=3.5, ratio=0.3),
+    "ard1": dict(family="ard", variances=(1.3,), lengthscales=((2.0,),)),
+    "ard1x2": dict(family="ard", variances=(1.3, 0.4), lengthscales=((2.0,), (7.0,))),
+    "ard2": dict(family="ard", variances=(1.3,), lengthscales=((2.0, 3.0),)),
+    "ard2x2": dict(family="ard", variances=(1.3, 0.4), lengthscales=((2.0, 3.0), (7.0, 5.0))),
+    "ard3": dict(family="ard", variances=(1.3,), lengthscales=((2.0, 3.0, 1.5),)),
+    "ard3x2": dict(family="ard", variances=(1.3, 0.4), lengthscales=((2.0, 3.0, 1.5), (7.0, 5.0, 6.0))),
+}
+
+
+@pytest.mark.parametrize("name", list(RAW_KERNELS))
+@pytest.mark.parametrize("na,nb", [(1, 1), (37, 100), (130, 64)])
+def test_assemble_writes_its_whole_buffer(name, na, nb):
+    """gp2d_assemble through the raw ABI into a NaN-filled padded buffer, at a single point, ragged
+    tiles and a second component that starts past a 64-point tile: no entry is left unwritten,
+    padded rows and columns are exact zeros (symmetric = 0) or identity rows (symmetric = 1),
+    diag_add sits on the valid diagonal (assemble_cases.check_whole_buffer).  The valid ARD entries
+    against the difference-based oracle, at the assembly tolerance of this file."""
+    import assemble_cases as AC
+    ks = E.KernelSpec(**RAW_KERNELS[name])
+    rng = np.random.default_rng(na * 1000 + nb)
+    xa = rng.uniform(0, 10, (na, ks.input_dim))
+    xb = rng.uniform(0, 10, (nb, ks.input_dim))
+    K = AC.check_whole_buffer(ks, xa, xb)
+    if ks.family == "ard":
+        assert rel(K, O.ard_rbf_exact(xa, xb, ks.variances, ks.lengthscales)) < 1e-13
+
+
+@pytest.mark.parametrize("kind", ["df", "mixed"])
+@pytest.mark.parametrize("npts", [100, 37])
+def test_assemble_cols_alone(kind, npts):
+    """gp2d_assemble_cols (the distributed fit's column slabs) on its own: 100 points (n_pad = 128,
+    n = 256) and 37 (n_pad = 64), every 64-aligned column range inside one component
+    (assemble_cases.check_cols_alone)."""
+    import assemble_cases as AC
+    x, _ = tracks(npts, seed=npts + 5)
+    AC.check_cols_alone(E.KernelSpec(kind=kind, l_df=5.0, l_cf=4.0, ratio=0.5 if kind == "mixed" else 1.0), x)
+
+
 @pytest.mark.parametrize("ntr,m,kind", [(16, 64, "df"), (100, 300, "mixed"), (256, 1000, "cf"), (700, 2500, "df")])
 def test_fit_predict_matches_oracle(ntr, m, kind):
     x, y = tracks(ntr, seed=ntr)

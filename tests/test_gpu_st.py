@@ -51,6 +51,26 @@ def test_st_assemble(kind, ratio, na, nb):
                                        rel=1e-15)
 
 
+def _st_points(n, seed):
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.uniform(0, 3, n), rng.uniform(0, 10, n), rng.uniform(0, 10, n)], 1)
+
+
+@pytest.mark.parametrize("na,nb", [(1, 1), (37, 100), (130, 64)])
+def test_st_assemble_writes_its_whole_buffer(na, nb):
+    """test_gpu_parity.test_assemble_writes_its_whole_buffer for the 3-coordinate points of the
+    spatio-temporal product (mixed kind, unequal lengths)."""
+    import assemble_cases as AC
+    AC.check_whole_buffer(spec("mixed", 0.3, l_df=2.5, l_cf=3.5), _st_points(na, na + 7 * nb), _st_points(nb, nb))
+
+
+@pytest.mark.parametrize("npts", [100, 37])
+def test_st_assemble_cols_alone(npts):
+    """test_gpu_parity.test_assemble_cols_alone for the spatio-temporal product."""
+    import assemble_cases as AC
+    AC.check_cols_alone(spec("mixed", 0.3, l_df=2.5, l_cf=3.5), _st_points(npts, npts + 5))
+
+
 @pytest.mark.parametrize("name", ["df", "mixed"])
 @pytest.mark.parametrize("engine", ["f64", "ozaki"])
 def test_st_golden_posterior(golden, name, engine):
