@@ -1282,7 +1282,9 @@ size_t gp2d_ozaki_wres_bytes(int64_t n) {
 
 static int launch_w_res(const double* W, int64_t n, WRows ldw, const OzakiConsts& oc, int8_t* wres,
                         const double* rowscale, hipStream_t s) {
-  ozaki_w_res_kernel<<<dim3((unsigned)(n / 64), (unsigned)(n / 256)), 256, 0, s>>>(W, n, ldw, oc, wres, rowscale);
+  // with the S planes of the three-product variance wherever this n has them (ozaki_host.hpp)
+  ozaki_w_res_kernel<<<dim3((unsigned)(n / 64), (unsigned)(n / 256)), 256, 0, s>>>(W, n, ldw, oc, wres, rowscale,
+                                                                                   oz_s_npad(n));
   return check_launch("ozaki_w_res_kernel");
 }
 
@@ -1448,6 +1450,13 @@ int gp2d_ozaki_guard_bits(double kss, double vmin, double target, int* wbits, in
 static int g_oz_skip = 1;
 void gp2d_ozaki_set_skip(int on) { g_oz_skip = on ? 1 : 0; }
 
+// ---- three block products instead of four (OzakiProducts, ozaki_host.hpp) wherever n allows it;
+// off: the four-product path everywhere.  K* planes made ahead carry the form of the setting they
+// were made under, so a predict must run under the same one.
+static int g_oz_three = 1;
+void gp2d_ozaki_set_three_products(int on) { g_oz_three = on ? 1 : 0; }
+static bool ozaki_three(int64_t n) { return g_oz_three && oz_s_npad(n) > 0; }
+
 // ---- the predict workspace (inline K* planes, or planes from gp2d_ozaki_kstar): its sizes here
 // and its pointers in predict_ozaki_impl both come from OzakiWork (ozaki_host.hpp)
 size_t gp2d_predict_ozaki_workspace(int64_t n, int64_t chunk) {
@@ -1478,10 +1487,20 @@ struct OzakiChunk {
 static int launch_kstar(const OzakiChunk& c, hipStream_t s, const double* xtr, int64_t ntr, int64_t npad,
                         const VecParams& vp, const double* alpha, const OzakiConsts& oc, int8_t* bres, double* pm,
                         uint8_t* flags) {
-  if ((uint64_t)(2 * npad) * (uint64_t)c.ncols < (1ull << 31))
-    ozaki_kstar_kernel<true><<<c.kgrid, 256, 0, s>>>(xtr, ntr, npad, c.xg, c.cv, c.cp, vp, alpha, oc, bres, pm, flags);
-  else
-    ozaki_kstar_kernel<false><<<c.kgrid, 256, 0, s>>>(xtr, ntr, npad, c.xg, c.cv, c.cp, vp, alpha, oc, bres, pm, flags);
+  // planes of (a − c, c, b − c) for the three-product GEMM, else (a, c, b)
+  const int form = !ozaki_three(2 * npad) ? KS_PLAIN : oc.pb <= 49 ? KS_DIFF_X : KS_DIFF_R;
+  const bool off32 = (uint64_t)(2 * npad) * (uint64_t)c.ncols < (1ull << 31);
+  auto launch = [&](auto off32_c, auto form_c) {
+    ozaki_kstar_kernel<decltype(off32_c)::value, decltype(form_c)::value>
+        <<<c.kgrid, 256, 0, s>>>(xtr, ntr, npad, c.xg, c.cv, c.cp, vp, alpha, oc, bres, pm, flags);
+  };
+  auto pick = [&](auto off32_c) {
+    if (form == KS_PLAIN) launch(off32_c, std::integral_constant<int, KS_PLAIN>{});
+    else if (form == KS_DIFF_X) launch(off32_c, std::integral_constant<int, KS_DIFF_X>{});
+    else launch(off32_c, std::integral_constant<int, KS_DIFF_R>{});
+  };
+  if (off32) pick(std::true_type{});
+  else pick(std::false_type{});
   return check_launch("ozaki_kstar_kernel");
 }
 
@@ -1532,10 +1551,15 @@ static int predict_ozaki_impl(const int8_t* wres, const double* rowscale, int nm
     if (compute_var) {
       const double nv = 2.0 * (double)ntr;
       TimedLaunch timed(s, 2.0 * (double)cv * nv * nv);  // FP64-equivalent algorithmic flop
-      // small n: every modulus in one launch (moduli on grid.z: no launch gap and no tail
-      // between the moduli, −3 % per chunk at n = 2048, profiles/r04_zbatch.txt); large n:
-      // one launch per modulus (the same within 0.2 %)
-      const int zper = (n <= kIgemmZBatchMaxN) ? nm : 1;
+      // The chunk's block products (OzakiProducts: three where n allows, else four in one launch),
+      // each over the moduli.  Four products, small n: every modulus in one launch (moduli on
+      // grid.z: no launch gap and no tail between the moduli, −3 % per chunk at n = 2048,
+      // profiles/r04_zbatch.txt); large n: one launch per modulus (the same within 0.2 %).  Three
+      // products: always every modulus in one launch per product — three shorter launches per
+      // modulus would each end in a tail of their own (measured)
+      const bool three = ozaki_three(n);
+      const OzakiProducts prods(n, cp, three);
+      const int zper = (three || n <= kIgemmZBatchMaxN) ? nm : 1;
       for (int l0 = 0; l0 < nm; l0 += zper) {
         const int nz = std::min(zper, nm - l0);
         IgemmZ zb{(int64_t)n * n, (int64_t)bplane, (int64_t)n * ncols, {}};
@@ -1543,15 +1567,16 @@ static int predict_ozaki_impl(const int8_t* wres, const double* rowscale, int nm
         // 256 output columns per workgroup, one workgroup per CU (the 128-wide shape with two
         // workgroups per CU measured −5 %: tools/microbench/igemm_bench.hip)
         constexpr int tbn = 256, nst = I_NSTAGE;
-        const dim3 ggrid((unsigned)(ncols / tbn), (unsigned)(n / IBM), (unsigned)nz);
         const int8_t* Al = wres + (size_t)l0 * n * n;
         const int8_t* Bl = B + (size_t)l0 * bplane;
         uint8_t* Cl = cres + (size_t)l0 * n * ncols;
-        igemm_nt_mod_kernel<tbn, nst><<<ggrid, 2 * tbn, 0, s>>>(Al, Bl, Cl, n, (int)n, (int)ncols, (int)n, 1, oc.m[l0],
-                                                                (int)(cp / IBN), (int)(ntr_pad / IBK),
-                                                                use_skip ? slist : nullptr, use_skip ? scnt : nullptr,
-                                                                zb);
-        GP2D_CHECK(check_launch("igemm_nt_mod_kernel"));
+        for (int q = 0; q < prods.count; ++q) {
+          const dim3 ggrid(prods.gx[q], prods.gy[q], (unsigned)nz);
+          igemm_nt_mod_kernel<tbn, nst><<<ggrid, 2 * tbn, 0, s>>>(Al, Bl, Cl, n, kslabs, oc.m[l0], prods.prod[q],
+                                                                  use_skip ? slist : nullptr,
+                                                                  use_skip ? scnt : nullptr, zb);
+          GP2D_CHECK(check_launch("igemm_nt_mod_kernel"));
+        }
       }
       timed.stop();
       const dim3 cgrid((unsigned)((ncols + OZ_CRT_BCOLS - 1) / OZ_CRT_BCOLS), (unsigned)npseg);

@@ -17,6 +17,7 @@
 //      2^-p scaling error; the squares are summed per column in a fixed order.
 // Parity is gated by the same 1e-10 tests as the FP64 path (tests/test_gpu_ozaki.py).
 #pragma once
+#include <climits>
 #include <type_traits>
 #include "common.hpp"
 #include "assemble.hpp"
@@ -156,63 +157,102 @@ __device__ __forceinline__ int ozaki_row_exp(double rowscale_i, const OzakiConst
 }
 
 // Pass 2: residue planes Wres[l] (int8, slab-blocked, zeros above the diagonal).  One
-// workgroup per (256-row block bi, 64-wide k slab ks) with ks < 4·(bi+1) (the GEMM, a_lower,
-// never reads past its diagonal tile): a wave covers 4 rows × 64 k per step — 16 lanes per row,
+// workgroup per (256-row block bi, 64-wide k slab ks) with ks < 4·(bi+1) (the GEMM never reads
+// past a row block's diagonal tile): a wave covers 4 rows × 64 k per step — 16 lanes per row,
 // 4 consecutive k per lane, 32 B of each row read contiguously — and writes, per modulus, the
 // 4 rows' 64-B runs of the slab tile: 256 contiguous bytes per wave store (the per-row form
 // wrote four 64-B pieces 16 KB apart).
+//
+// s_npad > 0 (a multiple of 256; n = 2·s_npad): the planes also carry S = W_L + W_R of the
+// v-observation rows for the three-product variance (ozaki_host.hpp, WresLayout).  The workgroup
+// of a v-observation row block and slab ks < s_npad/64 then also does slab ks + s_npad/64 (whose
+// own workgroup returns), so both residues of a row's column pair (k, s_npad + k) are at hand:
+// S's residue is centred((r_L + r_R) mod m) — exact for either residue form, since only the
+// class mod m enters the product — stored at (row − s_npad, s_npad + k), above the diagonal.
+__device__ __forceinline__ void w_residues4(const double (&x)[4], const OzakiConsts& oc, int l, uint32_t (&r)[4]) {
+  const double m = oc.md[l], im = oc.inv_m[l];
+  if (oc.pw <= 50) {   // uniform: |x| < 2^50, one exact residue per modulus
+#pragma unroll
+    for (int u = 0; u < 4; ++u) r[u] = residue_low_m(x[u], x[u] + OZ_MAGIC52, m, im);
+  } else {             // |x| < 2^60: x = xh·2^26 + xl exactly (|xl| ≤ 2^25, |xh| < 2^35), and
+    //                    x ≡ rh·(2^26 mod m) + rl (mod m) with the centred residues rh, rl (|·| ≤ 128)
+    const double c = oc.c26[l];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const double xh = rint(ldexp(x[u], -OZ_SPLIT));
+      const double xl = x[u] - ldexp(xh, OZ_SPLIT);   // exact: an integer below 2^26 in magnitude
+      const double rh = fma(-m, rint(xh * im), xh), rl = fma(-m, rint(xl * im), xl);
+      const double t = fma(rh, c, rl);         // exact: |t| ≤ 128·128 + 128
+      r[u] = residue_low_m(t, t + OZ_MAGIC52, m, im);
+    }
+  }
+}
+__device__ __forceinline__ uint32_t pack4_lo(const uint32_t (&r)[4]) {
+  return pack22(pack2_lo(r[0], r[1]), pack2_lo(r[2], r[3]));
+}
+// centred (a + b) mod m of two centred residues (|a|, |b| ≤ 128 as two's-complement words): the
+// low byte is an int8 residue again (±128 only for m = 256, where both are 0x80)
+__device__ __forceinline__ uint32_t centred_sum(uint32_t a, uint32_t b, int m) {
+  int s = (int)a + (int)b;
+  const int half = m >> 1;
+  s -= (s > half) ? m : 0;
+  s += (s < -half) ? m : 0;
+  return (uint32_t)s;
+}
+
 __global__ __launch_bounds__(256) void ozaki_w_res_kernel(const double* __restrict__ W, int64_t n, WRows wr,
                                                           OzakiConsts oc, int8_t* __restrict__ wres,
-                                                          const double* __restrict__ rowscale) {
+                                                          const double* __restrict__ rowscale, int64_t s_npad) {
   const int64_t bi = blockIdx.y, ks = blockIdx.x;
   if (ks * 64 >= (bi + 1) * 256) return;
+  const int64_t hs = s_npad / 64;                     // slabs per component half
+  const bool fold = hs > 0 && bi * 256 >= s_npad;     // a v-observation row block: W_L, W_R and S here
+  if (fold && ks >= hs) return;
+  const bool right = fold && (ks + hs) * 64 < (bi + 1) * 256;   // the W_R slab reaches the diagonal tile
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t k0 = ks * 64 + 4 * (lane & 15);
   const int64_t plane = n * n;
-#pragma unroll 1
-  for (int it = 0; it < 16; ++it) {
-    const int64_t i = bi * 256 + wv * 64 + it * 4 + (lane >> 4);
-    const int si = ozaki_row_exp(rowscale[i], oc);
-    const double* w = W + wr.off(i) + k0;
+  // the four scaled integers of row i from column kc (zeros past the diagonal and the stored row)
+  auto scaled4 = [&](int64_t i, int64_t kc, int si, double (&x)[4]) {
+    const double* w = W + wr.off(i) + kc;
     d2 p0 = {0.0, 0.0}, p1 = {0.0, 0.0};
-    if (k0 < wr.len(i, n)) {   // k0 and the row length are multiples of 4: all four or none stored
+    if (kc < wr.len(i, n)) {   // kc and the row length are multiples of 4: all four or none stored
       p0 = *reinterpret_cast<const d2*>(w);
       p1 = *reinterpret_cast<const d2*>(w + 2);
     }
     const double v[4] = {p0.x, p0.y, p1.x, p1.y};
-    double x[4], xm[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      x[u] = (k0 + u <= i) ? rint(ldexp(v[u], si)) : 0.0;
-      xm[u] = x[u] + OZ_MAGIC52;
-    }
+    for (int u = 0; u < 4; ++u) x[u] = (kc + u <= i) ? rint(ldexp(v[u], si)) : 0.0;
+  };
+#pragma unroll 1
+  for (int it = 0; it < 16; ++it) {
+    const int64_t i = bi * 256 + wv * 64 + it * 4 + (lane >> 4);
+    const int si = ozaki_row_exp(rowscale[i], oc);
+    double x[4];
+    scaled4(i, k0, si, x);
     int8_t* dst = wres + slab_offset(i, k0, n);
-    if (oc.pw <= 50) {   // uniform: |x| < 2^50, one exact residue per modulus
+    if (!fold) {
       for (int l = 0; l < oc.nmod; ++l) {
-        const double m = oc.md[l], im = oc.inv_m[l];
         uint32_t r[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) r[u] = residue_low_m(x[u], xm[u], m, im);
-        *reinterpret_cast<uint32_t*>(dst + (int64_t)l * plane) = pack22(pack2_lo(r[0], r[1]), pack2_lo(r[2], r[3]));
+        w_residues4(x, oc, l, r);
+        *reinterpret_cast<uint32_t*>(dst + (int64_t)l * plane) = pack4_lo(r);
       }
-    } else {             // |x| < 2^60: x = xh·2^26 + xl exactly (|xl| ≤ 2^25, |xh| < 2^35), and
-      //                    x ≡ rh·(2^26 mod m) + rl (mod m) with the centred residues rh, rl (|·| ≤ 128)
-      double xh[4], xl[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        xh[u] = rint(ldexp(x[u], -OZ_SPLIT));
-        xl[u] = x[u] - ldexp(xh[u], OZ_SPLIT);   // exact: an integer below 2^26 in magnitude
-      }
+    } else {
+      double xr[4] = {0.0, 0.0, 0.0, 0.0};
+      if (right) scaled4(i, s_npad + k0, si, xr);
+      int8_t* dst_r = wres + slab_offset(i, s_npad + k0, n);
+      int8_t* dst_s = wres + slab_offset(i - s_npad, s_npad + k0, n);
       for (int l = 0; l < oc.nmod; ++l) {
-        const double m = oc.md[l], im = oc.inv_m[l], c = oc.c26[l];
-        uint32_t r[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const double rh = fma(-m, rint(xh[u] * im), xh[u]), rl = fma(-m, rint(xl[u] * im), xl[u]);
-          const double t = fma(rh, c, rl);         // exact: |t| ≤ 128·128 + 128
-          r[u] = residue_low_m(t, t + OZ_MAGIC52, m, im);
+        uint32_t r[4], q[4] = {0u, 0u, 0u, 0u};
+        w_residues4(x, oc, l, r);
+        *reinterpret_cast<uint32_t*>(dst + (int64_t)l * plane) = pack4_lo(r);
+        if (right) {
+          w_residues4(xr, oc, l, q);
+          *reinterpret_cast<uint32_t*>(dst_r + (int64_t)l * plane) = pack4_lo(q);
         }
-        *reinterpret_cast<uint32_t*>(dst + (int64_t)l * plane) = pack22(pack2_lo(r[0], r[1]), pack2_lo(r[2], r[3]));
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q[u] = centred_sum(r[u], q[u], oc.m[l]);
+        *reinterpret_cast<uint32_t*>(dst_s + (int64_t)l * plane) = pack4_lo(q);
       }
     }
   }
@@ -247,7 +287,12 @@ template <> struct packed_bytes<4> { typedef uint32_t type; };
 // OFF32: a plane (n·2·cp bytes) is below 2^31 (the launcher checks), so the stores are buffer
 // stores — the plane in a scalar buffer resource, the 32-bit offsets computed once per grid
 // point — instead of three 64-bit address additions per modulus.
-template <bool OFF32>
+// FORM: what the planes hold — KS_PLAIN (a, c, b), the four-product form, or the three-product
+// form (a − c, c, b − c), differences of the scaled integers: KS_DIFF_X forms them in fp64 (up to 49
+// K* bits: |·| < 2^50, one residue like any entry), KS_DIFF_R subtracts the two residues mod m (50
+// bits, where the difference would leave residue_low_m's range).
+enum { KS_PLAIN = 0, KS_DIFF_X = 1, KS_DIFF_R = 2 };
+template <bool OFF32, int FORM>
 __global__ __launch_bounds__(256, GP2D_KS_OCC) void ozaki_kstar_kernel(
     const double* __restrict__ xtr, int64_t ntr, int64_t npad, const double* __restrict__ xg, int64_t cv,
     int64_t cp, VecParams vp, const double* __restrict__ alpha, OzakiConsts oc, int8_t* __restrict__ bres,
@@ -310,7 +355,13 @@ __global__ __launch_bounds__(256, GP2D_KS_OCC) void ozaki_kstar_kernel(
       xi[0][u] = rint(k11[u] * scale);
       xi[1][u] = rint(k12[u] * scale);
       xi[2][u] = rint(k22[u] * scale);
-      nz = nz || xi[0][u] != 0.0 || xi[1][u] != 0.0 || xi[2][u] != 0.0;
+      if constexpr (FORM == KS_DIFF_X) {   // exact: integers below 2^50
+        xi[0][u] -= xi[1][u];
+        xi[2][u] -= xi[1][u];
+      }
+      // the flag covers what is stored: a stored difference is zero exactly when its operands are equal
+      if constexpr (FORM == KS_DIFF_R) nz = nz || xi[1][u] != 0.0 || xi[0][u] != xi[1][u] || xi[2][u] != xi[1][u];
+      else nz = nz || xi[0][u] != 0.0 || xi[1][u] != 0.0 || xi[2][u] != 0.0;
 #pragma unroll
       for (int e = 0; e < 3; ++e) xm[e][u] = xi[e][u] + OZ_MAGIC52;
     }
@@ -322,13 +373,22 @@ __global__ __launch_bounds__(256, GP2D_KS_OCC) void ozaki_kstar_kernel(
     for (int l = 0; l < oc.nmod; ++l) {
       const double m = oc.md[l], im = oc.inv_m[l];
       pk_t pk[3];
+      uint32_t r[3][PPL];   // |xi| < 2^50
+#pragma unroll
+      for (int e = 0; e < 3; ++e)
+#pragma unroll
+        for (int u = 0; u < PPL; ++u) r[e][u] = residue_low_m(xi[e][u], xm[e][u], m, im);
+      if constexpr (FORM == KS_DIFF_R) {
+#pragma unroll
+        for (int u = 0; u < PPL; ++u) {
+          r[0][u] = centred_sum(r[0][u], 0u - r[1][u], oc.m[l]);
+          r[2][u] = centred_sum(r[2][u], 0u - r[1][u], oc.m[l]);
+        }
+      }
 #pragma unroll
       for (int e = 0; e < 3; ++e) {
-        uint32_t r[PPL];   // |xi| < 2^pB
-#pragma unroll
-        for (int u = 0; u < PPL; ++u) r[u] = residue_low_m(xi[e][u], xm[e][u], m, im);
-        if constexpr (PPL == 2) pk[e] = (pk_t)pack2_lo(r[0], r[1]);
-        else pk[e] = (pk_t)pack22(pack2_lo(r[0], r[1]), pack2_lo(r[2], r[3]));
+        if constexpr (PPL == 2) pk[e] = (pk_t)pack2_lo(r[e][0], r[e][1]);
+        else pk[e] = (pk_t)pack22(pack2_lo(r[e][0], r[e][1]), pack2_lo(r[e][2], r[e][3]));
       }
       int8_t* plane = bres + (int64_t)l * pstride;
       if constexpr (OFF32) {   // buffer stores: the plane in a scalar resource, 32-bit offsets
@@ -476,13 +536,36 @@ __device__ __forceinline__ void vmwait_barrier(std::integral_constant<int, W>) {
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(P * W) : "memory");
 }
 
-// A: M×K plane, B: N×K plane (both slab-blocked); C: column-major N×M bytes (ldc ≥ M).
+// A, B: slab-blocked planes with kslabs 64-byte slabs per row; C: column-major bytes (ldc ≥ rows).
+// One launch computes one block product, described by an IgemmProd (below): output row block bi
+// (grid.y, heavy first) and column block blockIdx.x take
+//   C[c_col0 + j][256·bi + r] = (Σ_{t < k_of(bi)/64} A-tile(bi, a_slab0 + t) · B-tile(b_rb0 + bj, b_slab0 + t)
+//                                (+ C[add_col0 + j][256·bi + r])) mod m.
 // B tiles (256-row layout block rb ≥ alias_rb, k slab s < alias_ks) are read from
-// (rb − alias_rb, s + alias_ks): the K* planes store the (v,u) block only as its equal (u,v)
-// block.  alias_rb = INT_MAX disables the aliasing.
-// slist / scnt (optional, ozaki_slab_list_kernel, per 256-row B block): the K loop runs over
-// the listed slabs only — the others have an all-zero K* tile and add exactly nothing.  A tile
-// whose list is shorter than the ring's prologue runs dense.
+// (rb − alias_rb, s + alias_ks): the four-product K* planes store the (v,u) block only as its
+// equal (u,v) block.  alias_rb = INT_MAX disables the aliasing.
+// slist / scnt (optional, ozaki_slab_list_kernel, per 256-row B block over all kslabs slabs): the
+// K loop runs over the listed slabs only — the others have an all-zero K* tile and add exactly
+// nothing.  A product that starts at slab b_slab0 (a multiple of 4) takes the contiguous part of
+// the sorted list between the prefix counts at b_slab0 and at b_slab0 + k_of(bi)/64.  A tile
+// whose part is shorter than the ring's prologue runs dense.
+struct IgemmProd {
+  int bi0;            // first output row block: grid.y covers bi0 .. bi0 + gridDim.y − 1
+  int a_slab0;        // A's first slab
+  int a_fold;         // row blocks bi ≥ a_fold read A from layout row block bi − a_fold, from slab
+  int a_fold_slab0;   //   a_fold_slab0 on (the S planes of the v-observation rows); INT_MAX: none
+  int b_rb0;          // B layout block of column block 0
+  int b_slab0;        // B's first slab
+  int alias_rb, alias_ks;
+  int k_bi0, k_cap;   // k_of(bi) = min(k_cap, 256·(bi − k_bi0 + 1)): A lower-triangular from row block k_bi0
+  int c_col0;         // first output column
+  int add_col0;       // ≥ 0: the epilogue adds the residues stored at these columns; < 0: none
+  // one plain product over whole planes: K columns, lower-triangular A (row block bi needs
+  // k < 256·(bi+1)) or dense
+  static IgemmProd plain(int K, bool lower) {
+    return {0, 0, INT_MAX, 0, 0, 0, INT_MAX, 0, lower ? 0 : -(1 << 20), K, 0, -1};
+  }
+};
 //
 // Two shapes (TBN = output columns per workgroup; rows are always 256 = IBM):
 //   TBN = 256: 512 threads, 8 waves as 2×4, one workgroup per CU, 4-stage ring (128 KB).
@@ -504,13 +587,12 @@ struct IgemmZ {
   int64_t sA, sB, sC;
   int m[OZ_MAXMOD];
 };
-constexpr int64_t kIgemmZBatchMaxN = 4096;   // predict_ozaki_impl batches the moduli up to this n
+constexpr int64_t kIgemmZBatchMaxN = 4096;   // predict_ozaki_impl batches the four-product form's moduli up to this n
 
 template <int TBN, int NST>
 __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_kernel(
-    const int8_t* __restrict__ A, const int8_t* __restrict__ B, uint8_t* __restrict__ C, int64_t ldc, int M, int N,
-    int K, int a_lower, int modulus, int alias_rb, int alias_ks, const int* __restrict__ slist,
-    const int* __restrict__ scnt, const IgemmZ zb) {
+    const int8_t* __restrict__ A, const int8_t* __restrict__ B, uint8_t* C, int64_t ldc, int kslabs_i, int modulus,
+    const IgemmProd p, const int* __restrict__ slist, const int* __restrict__ scnt, const IgemmZ zb) {
   if (gridDim.z > 1) {
     A += blockIdx.z * zb.sA;
     B += blockIdx.z * zb.sB;
@@ -528,32 +610,38 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
   constexpr int PPW = AP + BPW;                // DMA pieces per wave per slab
   __shared__ __attribute__((aligned(16))) int8_t smem[NST * STG];
   const int bj = blockIdx.x;
-  const int bi = (int)(gridDim.y - 1 - blockIdx.y);   // heavy (long-K) row blocks first
+  const int bi = p.bi0 + (int)(gridDim.y - 1 - blockIdx.y);   // heavy (long-K) row blocks first
   const int i0 = bi * IBM, j0 = bj * TBN;
-  const int jb = j0 / IBN, jr = j0 % IBN;             // 256-row B layout block, row offset in it
-  const int ke = a_lower ? min(K, i0 + IBM) : K;
+  const int jb = p.b_rb0 + j0 / IBN, jr = j0 % IBN;   // 256-row B layout block, row offset in it
+  const int ke = min(p.k_cap, (bi - p.k_bi0 + 1) * IBM);
+  const bool afold = bi >= p.a_fold;
+  const int arb = afold ? bi - p.a_fold : bi, as0 = afold ? p.a_fold_slab0 : p.a_slab0;
   // the wave index as a scalar: LDS-DMA destinations (M0) and piece offsets without v_readfirstlane
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid / WC, wc = wid % WC;
   const int l16 = lane & 15, lq = lane >> 4;
-  const int64_t kslabs = K / IBK;
-  const int8_t* Ap = A + (int64_t)bi * kslabs * I_OP;   // this row block's slab tiles
-  const bool alias = jb >= alias_rb;
-  const int8_t* Bp = B + (int64_t)jb * kslabs * I_OP + jr * IBK;
-  const int8_t* Bq = B + ((int64_t)(alias ? jb - alias_rb : 0) * kslabs + alias_ks) * I_OP + jr * IBK;
+  const int64_t kslabs = kslabs_i;
+  // this row block's and this column block's slab tiles from the product's first slabs on: the K
+  // loop counts slabs t relative to them (A slab as0 + t against B slab b_slab0 + t)
+  const int8_t* Ap = A + ((int64_t)arb * kslabs + as0) * I_OP;
+  const bool alias = jb >= p.alias_rb;
+  const int alias_ks = p.alias_ks;
+  const int8_t* Bp = B + ((int64_t)jb * kslabs + p.b_slab0) * I_OP + jr * IBK;
+  const int8_t* Bq = B + ((int64_t)(alias ? jb - p.alias_rb : 0) * kslabs + alias_ks) * I_OP + jr * IBK;
   int nsl = ke / IBK;
-  const int* sl = nullptr;   // slab list of this B block (nullptr: dense K loop)
+  const int* sl = nullptr;   // this product's part of the B block's slab list (nullptr: dense K loop)
   if (slist != nullptr) {
-    const int c = scnt[(int64_t)jb * (kslabs / 4 + 1) + ke / IBM];
+    const int* cn = scnt + (int64_t)jb * (kslabs / 4 + 1) + p.b_slab0 / 4;
+    const int c0 = cn[0], c = cn[ke / IBM] - c0;
     if (c == 0 || c >= NST - 1) {
       nsl = c;
-      sl = slist + (int64_t)jb * kslabs;
+      sl = slist + (int64_t)jb * kslabs + c0;
     }
   }
 
-  // the accumulators start at a multiple of m above every |Σ_k a·b| ≤ K·128² (centred
+  // the accumulators start at a multiple of m above every |Σ_k a·b| ≤ k_cap·128² (centred
   // residues), so the sums leave the MFMAs non-negative and ≡ the true sums (mod m)
-  const int bias = (int)ozaki_acc_bias(K, modulus);   // the bit pattern of an unsigned value
+  const int bias = (int)ozaki_acc_bias(p.k_cap, modulus);   // the bit pattern of an unsigned value
   i4v acc[8][4];
 #pragma unroll
   for (int mi = 0; mi < 8; ++mi)
@@ -564,10 +652,13 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
   const int drow = lane >> 2, dchunk = lane & 3;
   // LDS-DMA through buffer descriptors over this row block's slab tiles (A) and the column
   // block's (B; Bq: the aliased (v,u) tiles): lane offsets fixed, the slab (ks·16 KB) in soffset
-  const int rec = (int)(kslabs * I_OP);
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Ap, (short)0, rec, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rBp = __builtin_amdgcn_make_buffer_rsrc((void*)Bp, (short)0, rec, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rBq = __builtin_amdgcn_make_buffer_rsrc((void*)Bq, (short)0, rec, 0x00020000);
+  // (the descriptors end with the row block's tiles; the loop stays below ke ≤ that)
+  const __amdgpu_buffer_rsrc_t rA =
+      __builtin_amdgcn_make_buffer_rsrc((void*)Ap, (short)0, (int)((kslabs - as0) * I_OP), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rBp =
+      __builtin_amdgcn_make_buffer_rsrc((void*)Bp, (short)0, (int)((kslabs - p.b_slab0) * I_OP), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rBq =
+      __builtin_amdgcn_make_buffer_rsrc((void*)Bq, (short)0, (int)((kslabs - alias_ks) * I_OP), 0x00020000);
   int voA[AP], voB[BPW];
 #pragma unroll
   for (int h = 0; h < AP; ++h) {
@@ -627,7 +718,8 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
   // step s − 1.  Through the constant address space it is a scalar load (s_load, counted by
   // lgkmcnt); a vector load would need vmcnt(0), which also drains the slabs in flight.
   typedef const __attribute__((address_space(4))) int* const_int_ptr;
-  auto slab = [&](int s) -> int { return sl ? ((const_int_ptr)sl)[min(s, nsl - 1)] : s; };
+  const int b_slab0 = p.b_slab0;   // listed slabs count from the plane's first slab
+  auto slab = [&](int s) -> int { return sl ? ((const_int_ptr)sl)[min(s, nsl - 1)] - b_slab0 : s; };
   if (nsl > 0) {
 #pragma unroll
     for (int q = 0; q < NST - 1; ++q) issue(slab(q), q);
@@ -714,26 +806,59 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
   uint8_t* T = reinterpret_cast<uint8_t*>(smem);
   constexpr int TP = IBM + 16;
   static_assert(TBN * TP <= NST * STG, "epilogue image fits the ring");
+  //
+  // Epilogue add (add_col0 ≥ 0): the tile's 64 KB of prior residues (an earlier product of the same
+  // sum, each < m) come into T first, by the 16-B runs the stores use — the ring is free by now.  A
+  // lane's four consecutive rows at one column are one dword of T, at the address it writes later,
+  // so each byte joins its accumulator before the one reduction: (prior + Σ) mod m.  The biased
+  // sum stays in ozaki_mod_u32's range: bias + |Σ| + prior < 2^15·k_cap + 2·256 ≤ 2^15·(2^17 − 256)
+  // + 512 < 2^32 for k_cap ≤ n < 131072 (the predict's requirement).
   const OzModConsts mc = ozaki_mod_consts(modulus);
+  constexpr int NP = (IBM * TBN / 16) / (TBN * 2);   // 16-B runs per thread
+  auto epilogue = [&](auto add_c) {
+    constexpr bool add = decltype(add_c)::value;
+    if constexpr (add) {
+      const uint8_t* Cp = C + (int64_t)(p.add_col0 + j0) * ldc + i0;
+      i4v pv[NP];
 #pragma unroll
-  for (int mi = 0; mi < 8; ++mi)
+      for (int q = 0; q < NP; ++q) {
+        const int id = tid + TBN * 2 * q;
+        pv[q] = __builtin_nontemporal_load(reinterpret_cast<const i4v*>(Cp + (int64_t)(id >> 4) * ldc + 16 * (id & 15)));
+      }
 #pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      uint32_t pk = 0;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) pk |= ozaki_mod_u32((uint32_t)acc[mi][ni][u], mc) << (8 * u);
-      const int rloc = wr * 128 + mi * 16 + 4 * lq;
-      const int cloc = wc * 64 + ni * 16 + l16;
-      *reinterpret_cast<uint32_t*>(T + cloc * TP + rloc) = pk;
+      for (int q = 0; q < NP; ++q) {
+        const int id = tid + TBN * 2 * q;
+        *reinterpret_cast<i4v*>(T + (id >> 4) * TP + 16 * (id & 15)) = pv[q];
+      }
+      __syncthreads();
     }
-  __syncthreads();
 #pragma unroll
-  for (int p = 0; p < (IBM * TBN / 16) / (TBN * 2); ++p) {
-    const int id = tid + TBN * 2 * p;
+    for (int mi = 0; mi < 8; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const int rloc = wr * 128 + mi * 16 + 4 * lq;
+        const int cloc = wc * 64 + ni * 16 + l16;
+        uint32_t* t = reinterpret_cast<uint32_t*>(T + cloc * TP + rloc);
+        uint32_t prior = 0;
+        if constexpr (add) prior = *t;
+        uint32_t pk = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          pk |= ozaki_mod_u32((uint32_t)acc[mi][ni][u] + ((prior >> (8 * u)) & 0xffu), mc) << (8 * u);
+        *t = pk;
+      }
+  };
+  if (p.add_col0 >= 0) epilogue(std::true_type{});
+  else epilogue(std::false_type{});
+  __syncthreads();
+  uint8_t* Cc = C + (int64_t)(p.c_col0 + j0) * ldc + i0;
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    const int id = tid + TBN * 2 * q;
     const int cloc = id >> 4, ch = id & 15;
     // non-temporal: the planes are read once, by the CRT, past L2 (+0.3–0.5 %, profiles/r05_ntstore_ab.txt)
     const i4v v = *reinterpret_cast<const i4v*>(T + cloc * TP + 16 * ch);
-    __builtin_nontemporal_store(v, reinterpret_cast<i4v*>(C + (int64_t)(j0 + cloc) * ldc + i0 + 16 * ch));
+    __builtin_nontemporal_store(v, reinterpret_cast<i4v*>(Cc + (int64_t)cloc * ldc + 16 * ch));
   }
 }
 

@@ -58,6 +58,52 @@ struct OzakiWork {
   }
 };
 
+// W residue planes (gp2d_ozaki_prepare*): per modulus one n × n slab-blocked plane holding the
+// lower triangle of W; the int8 GEMM never reads a row block past its diagonal tile.  With
+// npad = n/2 a multiple of 256 (a 256-row tile then never straddles the u- and v-observation
+// rows) the planes also carry S = W_L + W_R of the v-observation rows — row i, column k < npad:
+// W[i][k] + W[i][npad + k] — for the three-product variance, in the part of each plane that the
+// triangular product never reads: element (i − npad, npad + k), i.e. layout row blocks
+// 0 … npad/256 − 1, slabs npad/64 … n/64 − 1.  S of the u-observation rows is W_L itself.
+// 0: this n has no S region (the four-product path).  The choice depends on n alone, so planes
+// made ahead and the predict that consumes them agree without extra state.
+constexpr int64_t oz_s_npad(int64_t n) { return (n > 0 && n % (2 * IBM) == 0) ? n / 2 : 0; }
+
+// The block products of one chunk's variance GEMM V = W·K*ᵀ (n rows; cp grid points padded to
+// 256, columns [u-out | v-out]), in stream order, with their grids in tiles.
+//   four products (any n): one launch, V_u = W_L·a + W_R·c and V_v = W_L·c + W_R·b with the (v,u)
+//     block of K* read from its equal (u,v) block c;
+//   three products (oz_s_npad(n) > 0; K* planes hold a − c, c, b − c), S = W_L + W_R:
+//     P1 = S·c → V_v's columns;  P2 = W_L·(a − c), + P1 → V_u;  P3 = W_R·(b − c) on the
+//     v-observation rows (W_R is zero above them), + P1 in place → V_v.  P3 follows P2, which
+//     reads what P3 overwrites.  Residues add mod m, so V's residues are the four-product ones.
+struct OzakiProducts {
+  int count;
+  IgemmProd prod[3];
+  unsigned gx[3], gy[3];
+  OzakiProducts(int64_t n, int64_t cp, bool three) {
+    const int nb = (int)(n / IBM), nbh = (int)(cp / IBN), hs = (int)(n / 2 / IBK);
+    if (!three) {
+      count = 1;
+      prod[0] = IgemmProd::plain((int)n, true);
+      prod[0].alias_rb = nbh;
+      prod[0].alias_ks = hs;
+      gx[0] = 2u * nbh;
+      gy[0] = (unsigned)nb;
+      return;
+    }
+    const int nb2 = nb / 2, npad = (int)(n / 2), vcol = (int)cp;
+    count = 3;
+    //         bi0  a_slab0 a_fold  a_fold_slab0 b_rb0 b_slab0 alias_rb alias_ks k_bi0 k_cap c_col0 add_col0
+    prod[0] = {0,   0,      nb2,    hs,          0,    hs,     INT_MAX, 0,       0,    npad, vcol,  -1};
+    prod[1] = {0,   0,      INT_MAX, 0,          0,    0,      INT_MAX, 0,       0,    npad, 0,     vcol};
+    prod[2] = {nb2, hs,     INT_MAX, 0,          nbh,  hs,     INT_MAX, 0,       nb2,  npad, vcol,  vcol};
+    gx[0] = gx[1] = gx[2] = (unsigned)nbh;
+    gy[0] = gy[1] = (unsigned)nb;
+    gy[2] = (unsigned)nb2;
+  }
+};
+
 // regions in order without overlap (the total is the end of the last by construction), doubles on
 // 8 bytes, ints on 4, the planes' two regions empty exactly when the planes are not inline
 constexpr bool ozaki_work_ok(int64_t n, int64_t chunk, int nmod) {

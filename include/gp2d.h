@@ -335,6 +335,13 @@ size_t gp2d_predict_ozaki_workspace_nmod(int64_t n, int64_t chunk, int nmod);
  * a 256-row grid tile — exact, such slabs add nothing.  gp2d_ozaki_set_skip(0) runs them
  * dense (A/B measurement and the bit-identity test); default on.                       */
 void   gp2d_ozaki_set_skip(int on);
+/* Where ntr_pad is a multiple of 256 the variance GEMM forms V = W·K*ᵀ from three block products
+ * instead of four (K*'s (v,u) block equals its (u,v) block c: with S = W_L + W_R,
+ * V_u = S·c + W_L·(a − c), V_v = S·c + W_R·(b − c)); residues add mod m, so every output bit is
+ * the four-product one.  gp2d_ozaki_set_three_products(0) forces the four-product path (A/B
+ * measurement and the bit-identity test); default on.  K* planes from gp2d_ozaki_kstar carry the
+ * form of the setting they were made under: predict with them under the same setting.    */
+void   gp2d_ozaki_set_three_products(int on);
 /* Z-order (Morton) codes of n points (dim 2 or 3) in their bounding box, 21 bits per
  * coordinate (bbox: 6 doubles of device scratch).  The ozaki engine sorts training and grid
  * points by these codes so that all-zero K* tiles cluster into skippable slabs.          */

@@ -114,8 +114,8 @@ int main(int argc, char** argv) {
   const dim3 gg(nc / 256, n / IBM);
   auto gemms = [&](hipStream_t s) {
     for (int l = 0; l < nmod; ++l)
-      igemm_nt_mod_kernel<256, 4><<<gg, 512, 0, s>>>(dA, dB, dC + l * plane, n, n, nc, n, 1, 251 - 2 * l, 1 << 30, 0,
-                                                      nullptr, nullptr, IgemmZ{});
+      igemm_nt_mod_kernel<256, 4><<<gg, 512, 0, s>>>(dA, dB, dC + l * plane, n, n / IBK, 251 - 2 * l,
+                                                      IgemmProd::plain(n, true), nullptr, nullptr, IgemmZ{});
   };
   auto crt16 = [&](hipStream_t s) {
     ozaki_crt_colsq_kernel<<<dim3(nc / OZ_CRT_BCOLS, n / OZ_CRT_ROWS), 256, 0, s>>>(dR, n, nc, oc, drs, dP);

@@ -18,7 +18,8 @@ using namespace gp2d;
 #endif
 #ifndef IGEMM_KERNEL
 #define IGEMM_KERNEL igemm_nt_mod_kernel<IG_TBN, IG_NST>
-#define IGEMM_EXTRA , nullptr, nullptr, gp2d::IgemmZ{}   // dense K loop (no slab list), one modulus
+// the product kernel: one plain product (IgemmProd::plain), dense K loop (no slab list), one modulus
+#define IGEMM_ARGS dA, dB, dC, n, n / IBK, mod, gp2d::IgemmProd::plain(kx, low != 0), nullptr, nullptr, gp2d::IgemmZ{}
 #endif
 #ifndef IGEMM_EXTRA
 #define IGEMM_EXTRA
@@ -55,7 +56,10 @@ int main() {
 #else
   const dim3 gl = g;
 #endif
-  auto launch = [&]() { IGEMM_KERNEL<<<gl, IGEMM_THREADS>>>(dA, dB, dC, n, n, nc, kx, low, mod IGEMM_INV, 1 << 30, 0 IGEMM_EXTRA); };
+#ifndef IGEMM_ARGS   // the dev copies keep the earlier argument list
+#define IGEMM_ARGS dA, dB, dC, n, n, nc, kx, low, mod IGEMM_INV, 1 << 30, 0 IGEMM_EXTRA
+#endif
+  auto launch = [&]() { IGEMM_KERNEL<<<gl, IGEMM_THREADS>>>(IGEMM_ARGS); };
   for (int w = 0; w < 3; ++w) launch();
   (void)hipDeviceSynchronize();
   (void)hipEventRecord(e0);

@@ -38,13 +38,14 @@ int main() {
     const dim3 g(nc / 256, n / IBM), gz(nc / 256, n / IBM, nmod);
     auto per_mod = [&]() {
       for (int l = 0; l < nmod; ++l)
-        igemm_nt_mod_kernel<256, 4><<<g, 512>>>(dA + l * pa, dB + l * pb, dC1 + l * pc, n, n, nc, n, 1, mods[l],
-                                                1 << 30, 0, nullptr, nullptr, IgemmZ{});
+        igemm_nt_mod_kernel<256, 4><<<g, 512>>>(dA + l * pa, dB + l * pb, dC1 + l * pc, n, n / IBK, mods[l],
+                                                IgemmProd::plain(n, true), nullptr, nullptr, IgemmZ{});
     };
     auto batched = [&]() {
       IgemmZ zb{pa, pb, pc, {}};
       for (int l = 0; l < nmod; ++l) zb.m[l] = mods[l];
-      igemm_nt_mod_kernel<256, 4><<<gz, 512>>>(dA, dB, dC2, n, n, nc, n, 1, mods[0], 1 << 30, 0, nullptr, nullptr, zb);
+      igemm_nt_mod_kernel<256, 4><<<gz, 512>>>(dA, dB, dC2, n, n / IBK, mods[0], IgemmProd::plain(n, true), nullptr, nullptr,
+                                               zb);
     };
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
