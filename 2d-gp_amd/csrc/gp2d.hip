@@ -18,6 +18,7 @@
 #include "ozaki.hpp"
 #include "ozaki_host.hpp"
 #include "factor_host.hpp"
+#include "cv.hpp"
 #include "lml.hpp"
 #include "lml_host.hpp"
 #include "dfact.hpp"
@@ -32,6 +33,7 @@
 #include <cmath>
 #include <atomic>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -1874,6 +1876,101 @@ int gp2d_kernel_grad(const double* xa, int64_t na, const double* xb, int64_t nb,
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_kernel_grad_workspace(na, nb), "kernel_grad: workspace too small");
   return launch_pair_grad(k, xa, na, xb, nb, round_up(nb, PT_TILE), DenseWeights{dL_dK, ld, na, nb},
                           KernelGradWork(na, nb).at(work).partial, 1.0, false, grad_dev, S(stream));
+}
+
+// ------------------------------------------------------------------ cross-validation (cv.hpp)
+size_t gp2d_cv_points_workspace(int64_t n) { return (n > 0 && n % PT_TILE == 0) ? cv_points_bytes(n) : 0; }
+
+int gp2d_cv_points(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* y, int64_t ntr,
+                   int64_t npad, int bd, const int64_t* out_order, double* mean, double* var, double* cuv,
+                   double* lpd, double* summary, void* work, size_t work_bytes, void* stream) {
+  GP2D_REQUIRE(bd == 1 || bd == 2, "cv_points: bd must be 1 or 2");
+  GP2D_REQUIRE(npad > 0 && npad % PT_TILE == 0 && n == bd * npad,
+               "cv_points: n must be bd·npad with npad a positive multiple of 64");
+  GP2D_REQUIRE(ldw >= n, "cv_points: ldw below n");
+  GP2D_REQUIRE(ntr >= 1 && ntr <= npad, "cv_points: ntr must be 1..npad");
+  GP2D_REQUIRE(bd == 2 || cuv == nullptr, "cv_points: cuv must be NULL for bd = 1 (one component has no cross term)");
+  GP2D_REQUIRE(W && alpha && y && mean && var && lpd && summary, "cv_points: NULL argument");
+  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_cv_points_workspace(n), "cv_points: workspace too small");
+  hipStream_t s = S(stream);
+  const int64_t nseg = (n + CV_RSEG - 1) / CV_RSEG;
+  double* part = static_cast<double*>(work);
+  cv_point_partial_kernel<<<dim3((unsigned)((npad + 255) / 256), (unsigned)nseg), 256, 0, s>>>(W, ldw, n, npad, bd,
+                                                                                            part);
+  GP2D_CHECK(check_launch("cv_point_partial_kernel"));
+  cv_point_finish_kernel<<<1, 1024, 0, s>>>(part, nseg, npad, ntr, bd, alpha, y, out_order, mean, var, cuv, lpd,
+                                            summary);
+  return check_launch("cv_point_finish_kernel");
+}
+
+size_t gp2d_cv_groups_workspace(int64_t n, int64_t qpad, int ngroups) {
+  if (n <= 0 || n % PT_TILE || qpad <= 0 || qpad % NB || qpad > CV_MAX_Q || ngroups < 1) return 0;
+  return CvGroupWork(n, qpad, cv_groups_batch(n, qpad, ngroups)).total;
+}
+
+int gp2d_cv_groups(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* y, int64_t ntr,
+                   int64_t npad, int bd, const int64_t* gstart, const int64_t* gidx, int ngroups,
+                   const int64_t* out_order, double* mean, double* var, double* lpd_group, int* info_group,
+                   void* work, size_t work_bytes, void* stream) {
+  GP2D_REQUIRE(bd == 1 || bd == 2, "cv_groups: bd must be 1 or 2");
+  GP2D_REQUIRE(npad > 0 && npad % PT_TILE == 0 && n == bd * npad,
+               "cv_groups: n must be bd·npad with npad a positive multiple of 64");
+  GP2D_REQUIRE(ldw >= n, "cv_groups: ldw below n");
+  GP2D_REQUIRE(ntr >= 1 && ntr <= npad, "cv_groups: ntr must be 1..npad");
+  GP2D_REQUIRE(gstart != nullptr && ngroups >= 1, "cv_groups: no groups");
+  int64_t qmax = 0;
+  for (int g = 0; g < ngroups; ++g) {   // gstart is a host array: it sizes every launch
+    const int64_t cnt = gstart[g + 1] - gstart[g];
+    GP2D_REQUIRE(gstart[g] >= 0 && cnt >= 0, "cv_groups: gstart must start at 0 or above and not decrease");
+    if (bd * cnt > CV_MAX_Q) {
+      set_error("cv_groups: group " + std::to_string(g) + " has " + std::to_string(bd * cnt) +
+                " components, over GP2D_CV_MAX_Q = " + std::to_string(CV_MAX_Q));
+      return -2;
+    }
+    qmax = std::max(qmax, bd * cnt);
+  }
+  GP2D_REQUIRE(W && alpha && y && gidx && mean && var && lpd_group && info_group, "cv_groups: NULL argument");
+  const int64_t qpad = round_up(std::max<int64_t>(qmax, 1), NB);
+  int nb = std::min(CV_MAX_BATCH, ngroups);
+  while (nb >= 1 && (work == nullptr || CvGroupWork(n, qpad, nb).total > work_bytes)) --nb;
+  GP2D_REQUIRE(nb >= 1, "cv_groups: workspace too small for one group (gp2d_cv_groups_workspace)");
+  GP2D_REQUIRE(reinterpret_cast<uintptr_t>(work) % 16 == 0, "cv_groups: workspace must be 16-byte aligned");
+  hipStream_t s = S(stream);
+  const CvGroupWork lay(n, qpad, nb);
+  double* gram = work_at(work, lay.gram);
+  double* fac = work_at(work, lay.fac);
+  double* dinv = work_at(work, lay.dinv);
+  double* panel = work_at(work, lay.panel);
+  const int64_t blk = qpad * qpad;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (double* out : {mean, var}) {   // points in no group keep NaN
+    cv_fill_kernel<<<(unsigned)((bd * ntr + 255) / 256), 256, 0, s>>>(out, bd * ntr, nan);
+    GP2D_CHECK(check_launch("cv_fill_kernel"));
+  }
+  for (int g0 = 0; g0 < ngroups; g0 += nb) {
+    const int cnt = std::min(nb, ngroups - g0);
+    CvBatch bt;
+    for (int b = 0; b <= CV_MAX_BATCH; ++b) bt.start[b] = gstart[g0 + std::min(b, cnt)];
+    cv_gather_t_kernel<<<dim3((unsigned)(n / 64), (unsigned)(qpad / 64), (unsigned)cnt), 256, 0, s>>>(
+        W, ldw, n, npad, ntr, bd, gidx, bt, (int)qpad, panel);
+    GP2D_CHECK(check_launch("cv_gather_t_kernel"));
+    GemmParams p = gemm_params();   // the lower tiles of panel·panelᵀ, one batch entry per group
+    p.A = p.B = panel; p.lda = p.ldb = n; p.sA = p.sB = qpad * n;
+    p.C = gram; p.ldc = qpad; p.sC = blk;
+    p.M = p.N = (int)qpad; p.K = (int)n;
+    p.c_lower = 1;
+    GP2D_CHECK((launch_gemm<true, EPI_STORE>(p, cnt, s)));
+    cv_gram_finish_kernel<<<dim3((unsigned)(qpad / 16), (unsigned)(qpad / 16), (unsigned)cnt), 256, 0, s>>>(
+        gram, fac, bt, bd, (int)qpad);
+    GP2D_CHECK(check_launch("cv_gram_finish_kernel"));
+    GP2D_CHECK(gp2d_potrf_batched(fac, qpad, qpad, blk, cnt, dinv, info_group + g0, stream));
+    GP2D_CHECK(gp2d_trtri_batched(fac, qpad, qpad, blk, cnt, dinv, work_at(work, lay.trtri),
+                                  TrtriWork(qpad, cnt, false).total, stream));
+    cv_group_solve_kernel<<<(unsigned)cnt, 256, 0, s>>>(fac, bt, bd, (int)qpad, npad, ntr, gidx, alpha, y, out_order,
+                                                        mean, var, lpd_group + g0);
+    GP2D_CHECK(check_launch("cv_group_solve_kernel"));
+  }
+  return 0;
 }
 
 // ------------------------------------------------------------------ instrumentation

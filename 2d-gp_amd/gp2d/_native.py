@@ -20,6 +20,7 @@ VAR_LATENT, VAR_NOISY, VAR_CLIPPED = 0, 1, 2
 FIELD_DIVERGENCE, FIELD_VORTICITY = 1, 2
 COMM_INT32, COMM_FLOAT64 = 2, 8
 COMM_SUM, COMM_MAX, COMM_MIN = 0, 1, 2
+CV_MAX_Q = 1024          # GP2D_CV_MAX_Q: components per held-out group
 
 # every symbol declared in include/gp2d.h
 EXPORTS = (
@@ -40,6 +41,7 @@ EXPORTS = (
     "gp2d_morton_sort_workspace", "gp2d_morton_sort", "gp2d_gather_rows", "gp2d_obs_pad", "gp2d_lml", "gp2d_lml_grad_count",
     "gp2d_lml_grad_workspace", "gp2d_lml_grad",
     "gp2d_kernel_grad_count", "gp2d_kernel_grad_workspace", "gp2d_kernel_grad",
+    "gp2d_cv_points_workspace", "gp2d_cv_points", "gp2d_cv_groups_workspace", "gp2d_cv_groups",
     "gp2d_gemm", "gp2d_transpose", "gp2d_comm_id_bytes", "gp2d_comm_unique_id", "gp2d_comm_init",
     "gp2d_comm_destroy", "gp2d_comm_size", "gp2d_bcast", "gp2d_allgather", "gp2d_allreduce", "gp2d_sendrecv",
     "gp2d_stream_create_cumask", "gp2d_stream_destroy", "gp2d_status_flip",
@@ -147,6 +149,10 @@ _SIGS = {
     "gp2d_kernel_grad_count": (_I, [_KP]),
     "gp2d_kernel_grad_workspace": (_SZ, [_I64, _I64]),
     "gp2d_kernel_grad": (_I, [_P, _I64, _P, _I64, _KP, _P, _I64, _P, _P, _SZ, _P]),
+    "gp2d_cv_points_workspace": (_SZ, [_I64]),
+    "gp2d_cv_points": (_I, [_P, _I64, _I64, _P, _P, _I64, _I64, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "gp2d_cv_groups_workspace": (_SZ, [_I64, _I64, _I]),
+    "gp2d_cv_groups": (_I, [_P, _I64, _I64, _P, _P, _I64, _I64, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "gp2d_gemm": (_I, [_I, _I64, _I64, _I64, _D, _P, _I64, _P, _I64, _D, _P, _I64, _P]),
     "gp2d_transpose": (_I, [_P, _I64, _I64, _P, _P]),
     "gp2d_comm_id_bytes": (_SZ, []),

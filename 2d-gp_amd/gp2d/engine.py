@@ -551,6 +551,7 @@ def _finish_problem(st: _Staged, W: torch.Tensor, y, noise: float, diag_add: flo
             "gp2d_potrs_inv")
     gp = _make_fit(st, noise, W, alpha, Y, dev)
     gp.extra["status_dev"] = status   # info + guard statistics on the device (the job stream broadcasts it)
+    gp.extra["diag_add"] = float(diag_add)   # noise + jitter on K_y's diagonal (cv_points / cv_groups latent=True)
     del pwork
     err = None
     if variance == "ozaki":
@@ -1587,6 +1588,150 @@ def lml_device(gp: GPFit, eval_gradient: bool = False):
     N.check(L.gp2d_lml_grad(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
                             ctypes.byref(desc), _ptr(g), _ptr(work), wbytes, s), "gp2d_lml_grad")
     return out, g
+
+
+# ------------------------------------------------------------------ cross-validation
+CV_MAX_Q = N.CV_MAX_Q   # components of one held-out group (GP2D_CV_MAX_Q)
+
+
+def _cv_fit(gp: GPFit, entry: str):
+    """What both cross-validation entries need of a fit: W, α and the padded observations."""
+    if gp.W is None:
+        raise ValueError(f"{entry}: this fit holds no factor W (a receiving rank's planes-only fit); "
+                         "cross-validate on the rank that owns the fit")
+    if gp.y is None:
+        raise ValueError(f"{entry}: this fit carries no observations (it was not made by engine.fit)")
+    gp.check()
+    return gp.kernel.block_dim, gp.n_train, gp.n_pad, gp.n
+
+
+def _cv_diag_add(gp: GPFit) -> float:
+    """noise + jitter on K_y's diagonal (with a jitchol retry's extra jitter)."""
+    return float(gp.extra.get("diag_add", gp.noise)) + float(gp.extra.get("jitchol", 0.0))
+
+
+def _cv_scores(sum_lpd: float, sum_ru2: float, sum_rv2: float, sum_chi2: float, npts: int) -> dict:
+    m = max(int(npts), 1)
+    return dict(rmse_u=math.sqrt(sum_ru2 / m), rmse_v=math.sqrt(sum_rv2 / m), mean_lpd=sum_lpd / m,
+                msll_chi2=sum_chi2 / m)
+
+
+def _cv_obs(gp: GPFit, bd: int) -> torch.Tensor:
+    """The observations [u…, v…] in the caller's input order, from the fit's padded vector."""
+    ntr, npad = gp.n_train, gp.n_pad
+    yc = gp.y.view(bd, npad)[:, :ntr]
+    if gp.perm is None:
+        return yc.reshape(-1).clone()
+    out = torch.empty((bd, ntr), dtype=torch.float64, device=gp.device)
+    out[:, gp.perm] = yc
+    return out.reshape(-1)
+
+
+def cv_points(gp: GPFit, latent: bool = False) -> dict:
+    """Leave-one-point-out cross-validation of a fit without refitting (gp2d_cv_points; DESIGN.md
+    §3.9): for every training point the prediction of its observation (u and v together) from all
+    the other points.  Replaces one refit per held-out fix of the reference's train / test scoring
+    (krig.py:578-646).  Device tensors in the caller's input order: mean, var ([u…, v…]), cuv (the
+    u–v predictive covariance; None for a scalar family), lpd (log predictive density per point),
+    resid = y − mean; host floats rmse_u, rmse_v (0 for a scalar family), mean_lpd and msll_chi2 =
+    mean of rᵀ·P_ii·r (1 per component for a well-calibrated fit).  var is the variance of the
+    held-out observation; latent=True subtracts the noise + jitter of K_y's diagonal from it."""
+    bd, ntr, npad, n = _cv_fit(gp, "cv_points")
+    L, dev = N.lib(), gp.device
+    mean = torch.empty(bd * ntr, dtype=torch.float64, device=dev)
+    var = torch.empty(bd * ntr, dtype=torch.float64, device=dev)
+    cuv = torch.empty(ntr, dtype=torch.float64, device=dev) if bd == 2 else None
+    lpd = torch.empty(ntr, dtype=torch.float64, device=dev)
+    summary = torch.empty(4, dtype=torch.float64, device=dev)
+    wb = int(L.gp2d_cv_points_workspace(n))
+    work = _workspace(wb, dev)
+    N.check(L.gp2d_cv_points(_ptr(gp.W), n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.y), ntr, npad, bd,
+                             None if gp.perm is None else _ptr(gp.perm), _ptr(mean), _ptr(var),
+                             None if cuv is None else _ptr(cuv), _ptr(lpd), _ptr(summary), _ptr(work), wb,
+                             _stream_handle(dev)), "gp2d_cv_points")
+    resid = _cv_obs(gp, bd) - mean
+    if latent:
+        var -= _cv_diag_add(gp)
+    s = summary.cpu().tolist()
+    return dict(mean=mean, var=var, cuv=cuv, lpd=lpd, resid=resid, **_cv_scores(s[0], s[1], s[2], s[3], ntr))
+
+
+def _cv_groups_run(gp: GPFit, labels):
+    """cv_groups' device call: (mean, var, lpd, info, sorted unique ids, held-out point count, the
+    call's workspace, q_pad).  The workspace begins with the last batch's Gram blocks (q_pad²
+    doubles per group, in the order of the ids)."""
+    bd, ntr, npad, n = _cv_fit(gp, "cv_groups")
+    lab = np.asarray(_to_host(labels)).reshape(-1)
+    if lab.shape[0] != ntr or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"cv_groups: labels must be {ntr} integers (one per training point)")
+    lab = lab.astype(np.int64)
+    L, dev = N.lib(), gp.device
+    if gp.perm is not None:   # the fit's point i is input point perm[i]
+        lab = lab[gp.perm.cpu().numpy()]
+    held = np.flatnonzero(lab >= 0)
+    if held.size == 0:
+        raise ValueError("cv_groups: every label is negative (no group to hold out)")
+    order = held[np.argsort(lab[held], kind="stable")]   # the fit's indices, grouped by label
+    ids, counts = np.unique(lab[held], return_counts=True)
+    over = np.flatnonzero(bd * counts > CV_MAX_Q)
+    if over.size:
+        g = int(over[0])
+        raise ValueError(f"cv_groups: group {int(ids[g])} has {int(counts[g])} points ({bd * int(counts[g])} "
+                         f"components), over the cap of {CV_MAX_Q} components")
+    ng = int(ids.size)
+    gstart = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    qpad = (bd * int(counts.max()) + NB - 1) // NB * NB
+    gidx = torch.as_tensor(order.astype(np.int64), device=dev)
+    mean = torch.empty(bd * ntr, dtype=torch.float64, device=dev)
+    var = torch.empty(bd * ntr, dtype=torch.float64, device=dev)
+    lpd = torch.empty(ng, dtype=torch.float64, device=dev)
+    info = torch.empty(ng, dtype=torch.int32, device=dev)
+    wb = int(L.gp2d_cv_groups_workspace(n, qpad, ng))
+    work = _workspace(wb, dev)
+    N.check(L.gp2d_cv_groups(_ptr(gp.W), n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.y), ntr, npad, bd,
+                             gstart.ctypes.data_as(ctypes.c_void_p), _ptr(gidx), ng,
+                             None if gp.perm is None else _ptr(gp.perm), _ptr(mean), _ptr(var), _ptr(lpd),
+                             _ptr(info), _ptr(work), wb, _stream_handle(dev)), "gp2d_cv_groups")
+    return mean, var, lpd, info, ids, int(held.size), work, qpad
+
+
+def cv_groups(gp: GPFit, labels, latent: bool = False) -> dict:
+    """Leave-group-out cross-validation without refitting (gp2d_cv_groups): every group of points
+    that share a label (a drifter id, say) is predicted from all the other points.  Replaces one
+    refit per held-out drifter (laser_compare_interp.py's scoring; krig.getData(drop_drifters=)).
+    labels: N integers in the caller's input order, ids need not be dense; a negative label puts
+    the point in no group (NaN in mean, var and resid, excluded from the scores).  Returns device
+    tensors mean, var ([u…, v…], the marginal predictive variances), resid, lpd (the joint log
+    predictive density per group) beside `labels` (the sorted unique ids, numpy), and the host
+    scores of cv_points over the held-out points (mean_lpd = Σ lpd / points).  Raises ValueError
+    naming the group that has more than CV_MAX_Q components, LinAlgError for a group whose
+    precision block is not positive definite."""
+    mean, var, lpd, info, ids, nheld, work, _ = _cv_groups_run(gp, labels)
+    del work
+    bd, ntr, npad = gp.kernel.block_dim, gp.n_train, gp.n_pad
+    bad = np.flatnonzero(info.cpu().numpy())
+    if bad.size:
+        raise np.linalg.LinAlgError(f"cv_groups: the precision block of group {int(ids[int(bad[0])])} is not "
+                                    "positive definite (a failed or ill-conditioned fit)")
+    resid = _cv_obs(gp, bd) - mean
+    if latent:
+        var -= _cv_diag_add(gp)
+    # the scores over the held-out points, from the outputs: rᵀ·P_GG·r = α_Gᵀ·r per group
+    r = resid.view(bd, ntr)
+    a = gp.alpha.view(bd, npad)[:, :ntr]
+    if gp.perm is not None:
+        ac = torch.empty_like(r)
+        ac[:, gp.perm] = a
+        a = ac
+    keep = ~torch.isnan(r[0])
+    zero = torch.zeros((), dtype=torch.float64, device=gp.device)
+    ss = torch.stack([lpd.sum(), (r[0][keep] ** 2).sum(), (r[1][keep] ** 2).sum() if bd == 2 else zero,
+                      (a[:, keep] * r[:, keep]).sum()]).cpu().tolist()
+    return dict(mean=mean, var=var, resid=resid, lpd=lpd, labels=ids, **_cv_scores(ss[0], ss[1], ss[2], ss[3], nheld))
+
+
+def _to_host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
 
 
 def kernel_grad(kernel: KernelSpec, xa, dL_dK, xb=None, device=None) -> np.ndarray:

@@ -263,6 +263,27 @@ class Krig:
                                                fix=fix, jitter=self.jitter, device=self.device, seed=seed,
                                                maxiter=maxiter, messages=messages))
 
+    # ------------------------------------------------------------------ cross-validation
+    def cross_validate(self, groups=None, latent: bool = False) -> dict:
+        """Score the fit on its own training data without refitting (engine.cv_points /
+        cv_groups): every point (groups=None) or every group of points sharing an
+        integer label (a drifter id; negative = in no group) is predicted from all the others —
+        what the reference does by splitting, refitting and predicting (krig.py:578-646).
+        numpy results in the predict() conventions: mean, var, resid of shape (bd·N, 1) with
+        f[:N] = u and f[N:] = v in the input order; lpd per point, or per group beside `labels`;
+        cuv (N, 1) for points of a vector kernel; the floats rmse_u, rmse_v, mean_lpd, msll_chi2.
+        var is the held-out observation's variance; latent=True takes the noise off."""
+        self._check()
+        res = E.cv_points(self.gp, latent=latent) if groups is None else E.cv_groups(self.gp, groups, latent=latent)
+        out = {}
+        for k, v in res.items():
+            if isinstance(v, torch.Tensor):
+                v = _to_numpy(v)
+                out[k] = v if k == "lpd" else v[:, None]
+            else:
+                out[k] = v
+        return out
+
     # ------------------------------------------------------------------ state
     @property
     def param_array(self):
@@ -349,6 +370,7 @@ class Krig:
                          torch.as_tensor(np.ascontiguousarray(W), device=dev),
                          torch.as_tensor(np.ascontiguousarray(alpha), device=dev), Y, dev)
         gp.extra["jitchol"] = float(jitchol_used)
+        gp.extra["diag_add"] = float(self.noise + self.jitter)
         if self.variance == "ozaki":
             E.ozaki_prepare_guarded(gp, float(self.noise + (self.jitter + jitchol_used)))
         self.gp = gp
@@ -446,6 +468,7 @@ def _prepare(tracks, st, et, lalim, lolim, sample_step, skip, drop_drifters=()):
         latt, lont, vob, uob = boundData(latt, lalim, latt, lont, vob, uob)
     xob, yob = nad83(lont, latt)
     tob = np.repeat(time_h[:, None], latt.shape[1], axis=1)
+    dob = np.repeat(np.arange(latt.shape[1], dtype=np.int64)[None, :], latt.shape[0], axis=0)   # drifter column
     yob[np.where(np.isnan(lont))] = np.nan
     xob[np.where(np.isnan(lont))] = np.nan
     xob = (xob - x_ori) / 1000.0
@@ -463,13 +486,15 @@ def _prepare(tracks, st, et, lalim, lolim, sample_step, skip, drop_drifters=()):
     (to, tt), (yo, yt), (xo, xt) = pick(tob), pick(yob), pick(xob)
     (lat_o, lat_t), (lon_o, lon_t) = pick(latt), pick(lont)
     (uo, ut), (vo, vt) = pick(uob), pick(vob)
+    do, dt_ = pick(dob)
     vo_mask = np.where((~np.isnan(xo)) & (~np.isnan(yo)))
     vt_mask = np.where((~np.isnan(xt)) & (~np.isnan(yt)))
     o = [a[vo_mask][:, None] for a in (to, yo, xo, lat_o, lon_o, uo, vo)]
     t = [a[vt_mask][:, None] for a in (tt, yt, xt, lat_t, lon_t, ut, vt)]
     return dict(X=np.concatenate([o[0], o[1], o[2]], 1), LL_o=np.concatenate([o[0], o[3], o[4]], 1),
                 uo=o[5], vo=o[6], Xt=np.concatenate([t[0], t[1], t[2]], 1),
-                LL_t=np.concatenate([t[0], t[3], t[4]], 1), ut=t[5], vt=t[6])
+                LL_t=np.concatenate([t[0], t[3], t[4]], 1), ut=t[5], vt=t[6],
+                drifter_o=do[vo_mask], drifter_t=dt_[vt_mask])
 
 
 def kriging(st, et, lalim=(0, 0), lolim=(0, 0), sample_step=5, skip=5, nKernels=1, output="rbfModel",
@@ -518,7 +543,7 @@ def kriging(st, et, lalim=(0, 0), lolim=(0, 0), sample_step=5, skip=5, nKernels=
         k.save(output + tag + ".npz")
         models[tag] = k
     np.savez(output + ".npz", Xo=X, obs=obs_all, Xt=Xt, LL_o=d["LL_o"], LL_t=d["LL_t"], test_points=obst,
-             kernelType=kernelType)
+             kernelType=kernelType, drifter=d["drifter_o"])
     print("End of script, time : " + str(time.time() - t0))
     return models
 
@@ -626,6 +651,36 @@ def predictTest(filename, device=None):
     V, U, VV, UV = (np.concatenate(a, 0) for a in (V, U, VV, UV))
     np.savez(filename + "_test.npz", Xt=Xt, Vp=V, VpVar=VV, Up=U, UpVar=UV, test_points=obst)
     return V, U, VV, UV
+
+
+def crossValidate(filename, by="point", device=None):
+    """Score the model(s) saved by kriging() on their own training data without a refit
+    (Krig.cross_validate): by="point" leaves each observation out in turn, by="drifter" each
+    drifter's whole track (the drifter column kriging() stores beside the inputs).  What
+    predictTest + rmse (krig.py:578-646) measure on a held-out split — and
+    laser_compare_interp.py by dropping drifters — read off the one fit that uses every
+    observation.  Returns {model name: cross_validate dict} ('v' and 'u' for kernelType 1, the
+    vector model's tag otherwise) and writes filename+'_cv.npz' with their scalar scores."""
+    if by not in ("point", "drifter"):
+        raise ValueError("by must be 'point' or 'drifter'")
+    f = np.load(filename + ".npz", allow_pickle=False)
+    kt = int(f["kernelType"]) if "kernelType" in f.files else 1
+    groups = None
+    if by == "drifter":
+        if "drifter" not in f.files:
+            raise ValueError(f"{filename}.npz carries no drifter column (written before crossValidate); "
+                             "run kriging() again")
+        groups = np.asarray(f["drifter"], dtype=np.int64).reshape(-1)
+    tags = ("_v", "_u") if kt == 1 else ({2: "_divFree", 3: "_curlFree", 4: "_combined"}[kt],)
+    out, scores = {}, {}
+    for tag in tags:
+        res = Krig.load(filename + tag + ".npz", device=device).cross_validate(groups=groups)
+        name = tag[1:] if kt == 1 else tag
+        out[name] = res
+        for k in ("rmse_u", "rmse_v", "mean_lpd", "msll_chi2"):
+            scores[f"{name.lstrip('_')}_{k}"] = res[k]
+    np.savez(filename + "_cv.npz", by=by, **scores)
+    return out
 
 
 def _prior_window(fm, tcenter, tlim, xlim, xrange, varname):

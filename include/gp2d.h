@@ -435,6 +435,53 @@ int    gp2d_kernel_grad(const double* xa, int64_t na, const double* xb, int64_t 
                         const gp2d_kernel_t* k, const double* dL_dK, int64_t ld,
                         double* grad_dev, void* work, size_t work_bytes, void* stream);
 
+/* ---- cross-validation of a fit without refitting ------------------------
+ * Replaces the train / test refits of the reference: krig.py:578-646 (predictTest, getRMSE, rmse
+ * split the tracks, fit the training part and predict the held-out part) and the held-out-drifter
+ * scoring of laser_compare_interp.py (one refit per left-out drifter).  With P = K_y⁻¹ = WᵀW and
+ * α = P·y, the observations y_G of any index set G given all the others are Gaussian with mean
+ * y_G − P_GG⁻¹·α_G and covariance P_GG⁻¹ (Rasmussen & Williams §5.4.2, block form): the fit holds
+ * every held-out prediction.  Both entries read only (W, alpha, y) — W, alpha as for gp2d_predict,
+ * y the padded observation vector of gp2d_potrs_inv — so they serve every kernel family and both
+ * variance engines.  bd = 1 | 2 components per point, n = bd·npad, component c of point i is
+ * column c·npad + i.  The variances are those of the held-out OBSERVATION (noise included).
+ * mean, var: bd·ntr doubles, [u…, v…] like a predict's outputs; out_order (optional, int64[ntr]):
+ * the results of point i of the fit's order go to position out_order[i] (a Morton-ordered fit's
+ * permutation); NULL: the fit's own order.  No atomics, fixed summation order: repeat calls give
+ * the same bits.
+ * gp2d_cv_points: leave one point out (its u and v together).  P_ii is the 2 × 2 Gram of the
+ *   point's two columns of W: one pass over W's lower triangle.  cuv (ntr doubles; may be NULL,
+ *   must be NULL for bd = 1): the predictive covariance of u and v; lpd (ntr): the log predictive
+ *   density of the held-out observation; summary (4 device doubles): Σ lpd, Σ r_u², Σ r_v²,
+ *   Σ rᵀ·P_ii·r with r = y_i − mean_i (r_v = 0 for bd = 1).  Workspace gp2d_cv_points_workspace(n)
+ *   bytes (0 for a bad n).
+ * gp2d_cv_groups: leave a group of points out.  Groups as CSR: group g holds the points
+ *   gidx[gstart[g] .. gstart[g+1]) (indices in the fit's order, each point in at most one group);
+ *   gstart is a HOST array of ngroups + 1 entries (it sizes the launches), gidx a device array.
+ *   Per group the q_g = bd·|g| columns are gathered, P_GG = W[:,G]ᵀ·W[:,G] is formed on the FP64
+ *   matrix cores (2n·q_pad² flop per group; the full WᵀW is never formed) into an exactly
+ *   symmetric q_pad × q_pad block with identity padding, q_pad = max q_g rounded up to 128, and
+ *   factored and inverted by the batched factor (≤ 64 groups per batch, batches sized by the
+ *   workspace).  q_g ≤ GP2D_CV_MAX_Q.  Points in no group get NaN in mean and var.  lpd_group
+ *   (ngroups device doubles): the joint log predictive density of each group; info_group (ngroups
+ *   device ints): LAPACK-style status of each block (k > 0: P_GG is not positive definite — a
+ *   point listed twice, an index outside [0, ntr), a failed fit; that group's outputs are void).
+ *   Workspace gp2d_cv_groups_workspace(n, qpad, ngroups) bytes, 16-byte aligned (0 unless qpad is a
+ *   multiple of 128 in [128, GP2D_CV_MAX_Q]); the entry accepts any size that holds one group and
+ *   fits its batches to it.  On return the workspace begins with the Gram blocks of the last
+ *   batch (q_pad² doubles each, in group order).                                              */
+size_t gp2d_cv_points_workspace(int64_t n);
+int gp2d_cv_points(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* y,
+                   int64_t ntr, int64_t npad, int bd, const int64_t* out_order,
+                   double* mean, double* var, double* cuv, double* lpd, double* summary,
+                   void* work, size_t work_bytes, void* stream);
+#define GP2D_CV_MAX_Q 1024   /* components per held-out group */
+size_t gp2d_cv_groups_workspace(int64_t n, int64_t qpad, int ngroups);
+int gp2d_cv_groups(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* y,
+                   int64_t ntr, int64_t npad, int bd, const int64_t* gstart, const int64_t* gidx,
+                   int ngroups, const int64_t* out_order, double* mean, double* var,
+                   double* lpd_group, int* info_group, void* work, size_t work_bytes, void* stream);
+
 /* ---- dense helpers (the GP_scripts functional API on explicit matrices) ------------
  * gp2d_gemm: C = alpha·A·op(B) + beta·C on the FP64 MFMA GEMM core; op(B) = B (transb = 0,
  *   B is k×n) or Bᵀ (transb = 1, B is n×k); row-major; m, n multiples of 128, k of 16 (the
