@@ -46,6 +46,12 @@ void set_error(const std::string& msg) { g_err = msg; }
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// The leading-dimension contract of include/gp2d.h ("Leading dimensions"): a matrix that any kernel
+// reads or writes in 16-byte pairs (d2 at base + row·ld + even column) needs an even ld and a
+// 16-byte aligned base; every other matrix only ld >= its row length.
+static inline bool ld_even(int64_t ld, int64_t row) { return ld >= row && ld % 2 == 0; }
+static inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
 // ---------------------------------------------------------------- timing hooks
 struct Timing {
   std::mutex mu;
@@ -142,7 +148,7 @@ static int assemble_impl(const double* xa, int64_t na, int64_t na_pad, const dou
   GP2D_REQUIRE(na <= na_pad && nb <= nb_pad && na >= 0 && nb >= 0, "point counts exceed padded counts");
   if (na_pad == 0 || nb_pad == 0) return 0;
   const int bd = is_vector_family(k) ? 2 : 1;
-  GP2D_REQUIRE(ld >= bd * nb_pad, "ld too small");
+  GP2D_REQUIRE(ld >= bd * nb_pad, "assemble: ld must be >= block_dim × nb_pad");
   GP2D_REQUIRE(symmetric >= 0 && symmetric <= ASM_LOWER, "symmetric must be 0, 1 or 2");
   GP2D_REQUIRE(symmetric != ASM_LOWER || (bd == 2 && xa == xb && na == nb && na_pad == nb_pad),
                "symmetric = 2 (lower block triangle) needs a vector kernel and xa == xb");
@@ -592,6 +598,7 @@ int potrf_impl(double* A, int64_t n, int64_t lda, double* dinv, int* info_dev, h
   GP2D_REQUIRE(lda >= n && lda % 2 == 0, "potrf: lda must be >= n and even");
   GP2D_REQUIRE(dinv != nullptr, "potrf: dinv buffer is required");
   GP2D_REQUIRE(nprob >= 1 && (nprob == 1 || (!fused && sA >= n * lda)), "potrf: bad problem batch");
+  GP2D_REQUIRE(aligned16(A), "potrf: A must be 16-byte aligned");
   const PotrfJob m{A, n, lda, nprob, sA};
   const int64_t sD = n * NB;   // one problem's diagonal inverses
   const int nb = (int)(n / NB);
@@ -739,8 +746,10 @@ size_t gp2d_trtri_workspace(int64_t n) { return TrtriWork(n, 1, true).total; }
 
 int gp2d_trtri(double* A, int64_t n, int64_t lda, const double* dinv, void* work, size_t work_bytes, void* stream) {
   GP2D_REQUIRE(n % NB == 0 && n > 0, "trtri: n must be a positive multiple of 128");
+  GP2D_REQUIRE(ld_even(lda, n), "trtri: lda must be >= n and even");
   const TrtriWork lay(n, 1, true);
   GP2D_REQUIRE(work != nullptr && work_bytes >= lay.total, "trtri: workspace too small");
+  GP2D_REQUIRE(aligned16(A), "trtri: A must be 16-byte aligned");
   hipStream_t s = S(stream);
   const int nb = (int)(n / NB);
   const TrtriWork::Ptrs w = lay.at(work);
@@ -762,7 +771,7 @@ int gp2d_trtri(double* A, int64_t n, int64_t lda, const double* dinv, void* work
 int gp2d_potrf_batched(double* A, int64_t n, int64_t lda, int64_t sA, int nprob, double* dinv, int* info_dev,
                        void* stream) {
   GP2D_REQUIRE(nprob >= 1 && nprob <= 64, "potrf_batched: nprob must be 1..64");
-  GP2D_REQUIRE(nprob == 1 || sA >= n * lda, "potrf_batched: problem stride below n·lda");
+  GP2D_REQUIRE(nprob == 1 || (sA >= n * lda && sA % 2 == 0), "potrf_batched: sA must be >= n·lda and even");
   return potrf_impl(A, n, lda, dinv, info_dev, S(stream), false, {}, nprob, nprob > 1 ? sA : 0);
 }
 
@@ -772,10 +781,12 @@ int gp2d_trtri_batched(double* A, int64_t n, int64_t lda, int64_t sA, int nprob,
                        size_t work_bytes, void* stream) {
   GP2D_REQUIRE(n % NB == 0 && n > 0, "trtri_batched: n must be a positive multiple of 128");
   GP2D_REQUIRE(nprob >= 1 && nprob <= 64, "trtri_batched: nprob must be 1..64");
-  GP2D_REQUIRE(nprob == 1 || sA >= n * lda, "trtri_batched: problem stride below n·lda");
+  GP2D_REQUIRE(ld_even(lda, n), "trtri_batched: lda must be >= n and even");
+  GP2D_REQUIRE(nprob == 1 || (sA >= n * lda && sA % 2 == 0), "trtri_batched: sA must be >= n·lda and even");
   GP2D_REQUIRE(dinv != nullptr, "trtri_batched: dinv (from gp2d_potrf_batched) is required");
   const TrtriWork lay(n, nprob, false);
   GP2D_REQUIRE(work != nullptr && work_bytes >= lay.total, "trtri_batched: workspace too small");
+  GP2D_REQUIRE(aligned16(A), "trtri_batched: A must be 16-byte aligned");
   hipStream_t s = S(stream);
   const int nb = (int)(n / NB);
   const TrtriWork::Ptrs w = lay.at(work);
@@ -795,10 +806,11 @@ size_t gp2d_dfact_panel_doubles(int64_t n) { return (size_t)(n > 0 ? n : 0) * DF
 
 size_t gp2d_dfact_workspace(int64_t n) { return DfactWork(n).total; }   // layout: factor_host.hpp
 
-static int dfact_args(const double* A, int64_t n, int64_t lda, int s) {
+static int dfact_args(const double* A, int64_t n, int64_t lda, int s, bool w = false) {
   GP2D_REQUIRE(A != nullptr, "dfact: NULL matrix");
   GP2D_REQUIRE(n > 0 && n % DF_SB == 0, "dfact: n must be a positive multiple of 512");
-  GP2D_REQUIRE(n <= INT32_MAX && lda >= n && lda % 2 == 0, "dfact: lda must be >= n and even");
+  GP2D_REQUIRE(n <= INT32_MAX && ld_even(lda, n),   // the parameter is ldw in the W-reading entries
+               w ? "dfact: ldw must be >= n and even" : "dfact: lda must be >= n and even");
   GP2D_REQUIRE(s >= 0 && (int64_t)s * DF_SB < n, "dfact: super-block index out of range");
   return 0;
 }
@@ -815,6 +827,7 @@ int gp2d_dfact_panel(double* A, int64_t n, int64_t lda, int s, double* panel, in
   GP2D_REQUIRE(panel != nullptr && info_dev != nullptr, "dfact_panel: NULL panel or info");
   const DfactWork lay(n);
   GP2D_REQUIRE(work != nullptr && work_bytes >= lay.total, "dfact_panel: workspace too small");
+  GP2D_REQUIRE(aligned16(A) && aligned16(panel), "dfact_panel: A and panel must be 16-byte aligned");
   hipStream_t st = S(stream);
   const int64_t s0 = (int64_t)s * DF_SB;
   double* As = A + s0 * lda + s0;                  // the super-column from its diagonal down
@@ -853,6 +866,7 @@ int gp2d_dfact_update(double* A, int64_t n, int64_t lda, int s, const double* pa
   int first, count;
   dfact_owned(std::max(t_lo, s + 1), std::min(t_hi, nsb), nranks, rank, first, count);
   if (count == 0) return 0;
+  GP2D_REQUIRE(aligned16(A) && aligned16(panel), "dfact_update: A and panel must be 16-byte aligned");
   // A[rows ≥ t·512, t] −= L21[t rows..] · L21[t block]ᵀ for the owned t, lower tiles only (K = 512)
   const int64_t r0 = (int64_t)(s + 1) * DF_SB;
   const double* L21 = panel + (int64_t)DF_SB * DF_SB;   // global row r0 + i at panel row i
@@ -874,6 +888,7 @@ int gp2d_dfact_invstep(double* A, int64_t n, int64_t lda, int s, const double* p
   GP2D_REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, "dfact_invstep: bad rank / world size");
   const DfactWork lay(n);
   GP2D_REQUIRE(work != nullptr && work_bytes >= lay.total, "dfact_invstep: workspace too small");
+  GP2D_REQUIRE(aligned16(A) && aligned16(panel), "dfact_invstep: A and panel must be 16-byte aligned");
   hipStream_t st = S(stream);
   const int64_t s0 = (int64_t)s * DF_SB;
   if (s % nranks == rank) {   // this rank's W column block s starts as the identity block column
@@ -913,7 +928,7 @@ int gp2d_dfact_invstep(double* A, int64_t n, int64_t lda, int s, const double* p
 }
 
 static int dfact_blocks_args(const double* W, int64_t n, int64_t ldw, int t0, int dt, int count) {
-  GP2D_CHECK(dfact_args(W, n, ldw, t0));
+  GP2D_CHECK(dfact_args(W, n, ldw, t0, true));
   GP2D_REQUIRE(count >= 1 && dt >= 1 && (int64_t)(t0 + (count - 1) * dt) * DF_SB < n,
                "dfact: super-column list out of range");
   return 0;
@@ -972,6 +987,7 @@ int gp2d_pack_lower(double* W, int64_t n, int64_t ldw, double* packed, int unpac
   GP2D_REQUIRE(W && packed, "pack_lower: NULL buffer");
   GP2D_REQUIRE(n > 0 && n % NB == 0 && ldw >= n && ldw % 2 == 0,
                "pack_lower: n must be a positive multiple of 128, ldw >= n and even");
+  GP2D_REQUIRE(aligned16(W) && aligned16(packed), "pack_lower: W and packed must be 16-byte aligned");
   const dim3 g((unsigned)((n + 511) / 512), (unsigned)(n / NB));
   if (unpack) pack_lower_kernel<true><<<g, 256, 0, S(stream)>>>(W, n, ldw, packed);
   else pack_lower_kernel<false><<<g, 256, 0, S(stream)>>>(W, n, ldw, packed);
@@ -981,6 +997,7 @@ int gp2d_pack_lower(double* W, int64_t n, int64_t ldw, double* packed, int unpac
 int gp2d_zero_upper(double* A, int64_t n, int64_t lda, void* stream) {
   GP2D_REQUIRE(A != nullptr && n > 0 && n % NB == 0 && lda >= n && lda % 2 == 0,
                "zero_upper: n must be a positive multiple of 128, lda >= n and even");
+  GP2D_REQUIRE(aligned16(A), "zero_upper: A must be 16-byte aligned");
   dim3 zg((unsigned)((n / 2 + 255) / 256), (unsigned)n);
   zero_upper_kernel<<<zg, 256, 0, S(stream)>>>(A, n, lda);
   return check_launch("zero_upper_kernel");
@@ -992,6 +1009,7 @@ size_t gp2d_potrs_workspace(int64_t n) { return PotrsWork(n).total; }
 int gp2d_potrs_inv(const double* W, int64_t n, int64_t ldw, const double* y, double* alpha, void* work,
                    size_t work_bytes, void* stream) {
   GP2D_REQUIRE(n % NB == 0 && n > 0, "potrs: n must be a positive multiple of 128");
+  GP2D_REQUIRE(ldw >= n, "potrs: ldw must be >= n");
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_potrs_workspace(n), "potrs: workspace too small");
   hipStream_t s = S(stream);
   const auto [z, part] = PotrsWork(n).at(work);
@@ -1113,11 +1131,13 @@ int gp2d_predict(const double* W, int64_t n, int64_t ldw, const double* alpha, c
   const int bd = gp2d_block_dim(k);
   GP2D_REQUIRE(n == bd * ntr_pad, "predict: n must equal block_dim × ntr_pad");
   GP2D_REQUIRE(n % NB == 0, "predict: n must be a multiple of 128");
+  GP2D_REQUIRE(ld_even(ldw, n), "predict: ldw must be >= n and even");
   GP2D_REQUIRE(chunk > 0 && chunk % PT_TILE == 0, "predict: chunk must be a positive multiple of 64");
   GP2D_REQUIRE(bd * chunk % GBN == 0, "predict: block_dim × chunk must be a multiple of 128");
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_predict_workspace(n, chunk, bd), "predict: workspace too small");
   GP2D_REQUIRE(var_mode >= 0 && var_mode <= 2, "predict: bad var_mode");
   if (m <= 0) return 0;
+  GP2D_REQUIRE(aligned16(W), "predict: W must be 16-byte aligned");
   hipStream_t s = S(stream);
   ChunkedPredict v;
   v.bd = bd;
@@ -1160,11 +1180,13 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
                "predict_field: field must be GP2D_FIELD_DIVERGENCE or GP2D_FIELD_VORTICITY");
   GP2D_REQUIRE(n == 2 * ntr_pad, "predict_field: n must equal 2 × ntr_pad");
   GP2D_REQUIRE(n % NB == 0 && n > 0, "predict_field: n must be a positive multiple of 128");
-  GP2D_REQUIRE(ntr >= 0 && ntr <= ntr_pad && ldw >= n, "predict_field: bad point count or ldw");
+  GP2D_REQUIRE(ntr >= 0 && ntr <= ntr_pad, "predict_field: bad point count");
+  GP2D_REQUIRE(ld_even(ldw, n), "predict_field: ldw must be >= n and even");
   GP2D_REQUIRE(chunk > 0 && chunk % GBN == 0, "predict_field: chunk must be a positive multiple of 128");
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_predict_field_workspace(n, chunk),
                "predict_field: workspace too small");
   if (m <= 0) return 0;
+  GP2D_REQUIRE(aligned16(W), "predict_field: W must be 16-byte aligned");
   hipStream_t s = S(stream);
   if (field_weight(k, field) == 0.0 && k->kind != GP2D_KIND_MIXED) {
     // div-free flow has no divergence, curl-free flow no vorticity: exact zeros, no GEMM
@@ -1209,12 +1231,14 @@ int gp2d_predict_grad(const double* W, int64_t n, int64_t ldw, const double* alp
   GP2D_REQUIRE(field_kernel_ok(k), "predict_grad: div-free, curl-free or mixed vector kernels only");
   GP2D_REQUIRE(n == 2 * ntr_pad, "predict_grad: n must equal 2 × ntr_pad");
   GP2D_REQUIRE(n % NB == 0 && n > 0, "predict_grad: n must be a positive multiple of 128");
-  GP2D_REQUIRE(ntr >= 0 && ntr <= ntr_pad && ldw >= n, "predict_grad: bad point count or ldw");
+  GP2D_REQUIRE(ntr >= 0 && ntr <= ntr_pad, "predict_grad: bad point count");
+  GP2D_REQUIRE(ld_even(ldw, n), "predict_grad: ldw must be >= n and even");
   GP2D_REQUIRE(chunk > 0 && chunk % PT_TILE == 0, "predict_grad: chunk must be a positive multiple of 64");
   GP2D_REQUIRE(n < (int64_t)1 << 30 && chunk < (int64_t)1 << 28, "predict_grad: n or chunk out of range");
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_predict_grad_workspace(n, chunk),
                "predict_grad: workspace too small");
   if (m <= 0) return 0;
+  GP2D_REQUIRE(aligned16(W), "predict_grad: W must be 16-byte aligned");
   hipStream_t s = S(stream);
   const GradEntry ge = make_grad_entry(k);
   // four columns per target in grad.hpp's layout; the 4 × 4 prior, no noise, no clipping; untimed
@@ -1239,7 +1263,8 @@ int gp2d_predict_cov(const double* W, int64_t n, int64_t ldw, const double* alph
   GP2D_REQUIRE(field_kernel_ok(k), "predict_cov: div-free, curl-free or mixed vector kernels only");
   GP2D_REQUIRE(n == 2 * ntr_pad, "predict_cov: n must equal 2 × ntr_pad");
   GP2D_REQUIRE(n % NB == 0 && n > 0, "predict_cov: n must be a positive multiple of 128");
-  GP2D_REQUIRE(ntr >= 0 && ntr <= ntr_pad && ldw >= n, "predict_cov: bad point count or ldw");
+  GP2D_REQUIRE(ntr >= 0 && ntr <= ntr_pad, "predict_cov: bad point count");
+  GP2D_REQUIRE(ld_even(ldw, n), "predict_cov: ldw must be >= n and even");
   GP2D_REQUIRE(m >= 0 && postcov_q(m) < (int64_t)1 << 30 && n < (int64_t)1 << 30,
                "predict_cov: m or n out of range");
   if (m == 0) return 0;
@@ -1247,6 +1272,7 @@ int gp2d_predict_cov(const double* W, int64_t n, int64_t ldw, const double* alph
   GP2D_REQUIRE(ldc >= q, "predict_cov: ldc must be at least q = 2·⌈m/64⌉·64");
   const PredictCovWork lay(n, m);
   GP2D_REQUIRE(work != nullptr && work_bytes >= lay.total, "predict_cov: workspace too small");
+  GP2D_REQUIRE(aligned16(W), "predict_cov: W must be 16-byte aligned");
   hipStream_t s = S(stream);
   const PredictCovWork::Ptrs w = lay.at(work);
 
@@ -1321,7 +1347,10 @@ static int prepare_finish(int nmod, const gp2d_kernel_t* k, int pw, int pb, cons
 
 int gp2d_ozaki_prepare(const double* W, int64_t n, int64_t ldw, const gp2d_kernel_t* k, int wbits, int kbits,
                        int8_t* wres, double* rowscale, int* nmod_out, void* stream) {
+  // ldw = 0 would select WRows' packed layout (gp2d_ozaki_prepare_packed's): refused here
+  GP2D_REQUIRE(ld_even(ldw, n), "ozaki: ldw must be >= n and even");
   GP2D_CHECK(prepare_args(k, wbits, kbits, n, true, nmod_out));
+  GP2D_REQUIRE(aligned16(W), "ozaki: W must be 16-byte aligned");
   const int pw = ozaki_wbits(wbits), pb = ozaki_kbits(kbits);
   hipStream_t s = S(stream);
   double* l1 = reinterpret_cast<double*>(wres);  // scratch: the planes are written afterwards
@@ -1366,13 +1395,14 @@ static int prepare_apriori(const double* W, int64_t n, WRows wr, const gp2d_kern
   // round trip); a violated bound could only come from a failed factor and is poisoned by CRT
   const int nmod = gp2d_ozaki_nmod_apriori(n, k, diag_add, pw, pb);
   GP2D_REQUIRE(nmod > 0, "ozaki: a-priori bound exceeds the modulus table");
+  GP2D_REQUIRE(aligned16(W), "ozaki: W (or the packed payload) must be 16-byte aligned");
   // no L1 norms (the count is a-priori): one pass over W for the row exponents, one for the planes
   return prepare_finish(nmod, k, pw, pb, W, n, wr, wres, rowscale, true, nmod_out, s);
 }
 
 int gp2d_ozaki_prepare_async(const double* W, int64_t n, int64_t ldw, const gp2d_kernel_t* k, double diag_add,
                              int wbits, int kbits, int8_t* wres, double* rowscale, int* nmod_out, void* stream) {
-  GP2D_REQUIRE(ldw >= n, "ozaki: ldw must be >= n");
+  GP2D_REQUIRE(ld_even(ldw, n), "ozaki: ldw must be >= n and even");
   return prepare_apriori(W, n, WRows{ldw}, k, diag_add, wbits, kbits, wres, rowscale, nmod_out, S(stream));
 }
 
@@ -1390,8 +1420,9 @@ size_t gp2d_ozaki_guard_workspace(int64_t n) {
 
 int gp2d_ozaki_guard(const double* W, int64_t n, int64_t ldw, int64_t ntr, int64_t npad, double diag_add,
                      double* stats, void* work, size_t work_bytes, void* stream) {
-  GP2D_REQUIRE(W && stats && n > 0 && ldw >= n && ntr >= 1 && npad >= ntr && (n == npad || n == 2 * npad),
+  GP2D_REQUIRE(W && stats && n > 0 && ntr >= 1 && npad >= ntr && (n == npad || n == 2 * npad),
                "ozaki_guard: bad arguments");
+  GP2D_REQUIRE(ldw >= n, "ozaki_guard: ldw must be >= n");
   // any δ: the formula is algebra on K = K_y − δI.  δ ≤ 0 (no noise, or a caller's negative
   // "noise") gives a latent variance ≤ 0 at the observations, where no precision bounds the
   // relative error — stats[0] ≤ 0 sends the fit to the FP64 engine
@@ -1772,7 +1803,8 @@ int gp2d_status_flip(int* status, int count, void* stream) {
 int gp2d_lml(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* y, int64_t nobs,
              double* lml_dev, void* stream) {
   GP2D_REQUIRE(W && alpha && y && lml_dev, "lml: NULL argument");
-  GP2D_REQUIRE(n > 0 && ldw >= n && nobs >= 0 && nobs <= n, "lml: bad sizes");
+  GP2D_REQUIRE(n > 0 && nobs >= 0 && nobs <= n, "lml: bad sizes");
+  GP2D_REQUIRE(ldw >= n, "lml: ldw must be >= n");
   hipStream_t s = S(stream);
   lml_terms_kernel<<<1, 256, 0, s>>>(W, n, ldw, alpha, y, nobs, lml_dev);
   return check_launch("lml_terms_kernel");
@@ -1845,8 +1877,10 @@ int gp2d_lml_grad(const double* W, int64_t n, int64_t ldw, const double* alpha, 
   const int bd = gp2d_block_dim(k);
   GP2D_REQUIRE(n == bd * ntr_pad && ntr_pad % PT_TILE == 0, "lml_grad: n must equal block_dim × ntr_pad");
   GP2D_REQUIRE(n % NB == 0, "lml_grad: n must be a multiple of 128");
-  GP2D_REQUIRE(ntr >= 1 && ntr <= ntr_pad && ldw >= n, "lml_grad: bad sizes");
+  GP2D_REQUIRE(ntr >= 1 && ntr <= ntr_pad, "lml_grad: bad sizes");
+  GP2D_REQUIRE(ld_even(ldw, n), "lml_grad: ldw must be >= n and even");
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_lml_grad_workspace(n), "lml_grad: workspace too small");
+  GP2D_REQUIRE(aligned16(W), "lml_grad: W must be 16-byte aligned");
   hipStream_t s = S(stream);
   const auto [Wt, C, partial] = LmlGradWork(n).at(work);
   // Wt = Wᵀ (upper), C = Wt·W = K_y⁻¹, lower tiles only
@@ -1980,8 +2014,11 @@ int gp2d_gemm(int transb, int64_t m, int64_t n, int64_t k, double alpha, const d
   GP2D_REQUIRE(A && B && C, "gemm: NULL argument");
   GP2D_REQUIRE(m % NB == 0 && n % NB == 0 && k % 16 == 0 && m >= 0 && n >= 0 && k >= 0,
                "gemm: m, n must be multiples of 128 and k of 16");
-  GP2D_REQUIRE(lda >= k && ldc >= n && ldb >= (transb ? k : n), "gemm: leading dimensions too small");
+  GP2D_REQUIRE(ld_even(lda, k), "gemm: lda must be >= k and even");
+  GP2D_REQUIRE(ld_even(ldb, transb ? k : n), "gemm: ldb must be >= B's row length (n, or k with transb) and even");
+  GP2D_REQUIRE(ldc >= n, "gemm: ldc must be >= n");
   GP2D_REQUIRE(m <= INT32_MAX && n <= INT32_MAX && k <= INT32_MAX, "gemm: sizes exceed int32");
+  GP2D_REQUIRE(aligned16(A) && aligned16(B), "gemm: A and B must be 16-byte aligned");
   GemmParams p = gemm_params();
   p.A = A; p.lda = lda;
   p.B = B; p.ldb = ldb;

@@ -23,6 +23,24 @@
  *   predictions     mean/var = [u_1..u_M, v_1..v_M] (GP_laser.py:134-136).
  * Padded training points carry identity rows in K_y and zero cross-covariance,
  * so they change nothing.
+ *
+ * Leading dimensions.  A matrix argument with a leading dimension (ld, lda, ldb, ldc, ldw; in
+ * doubles) may be a view into a larger buffer of the caller: element (i, j) is at base + i·ld + j,
+ * ld >= the row length, and no entry reads or writes a row's slack (columns past the row length)
+ * or anything outside the view.  Where a kernel moves the matrix in 16-byte pairs (the FP64 GEMM's
+ * operand loads, the diagonal-block and packing kernels) ld must also be EVEN and the base pointer
+ * 16-BYTE ALIGNED, so that every row starts on a 16-byte boundary; that is the rule unless the
+ * entry is listed here.  Entries that touch the matrix with 8-byte accesses only take ANY ld >= the
+ * row length and any (8-byte aligned) base:
+ *   gp2d_assemble / gp2d_assemble_cols (out), gp2d_potrs_inv, gp2d_ozaki_guard, gp2d_lml,
+ *   gp2d_kernel_grad (dL_dK: the reference's unpadded layout, bd·nb may be odd), gp2d_cv_points,
+ *   gp2d_cv_groups (W is gathered element-wise before the Gram product), gp2d_transpose (A),
+ *   gp2d_predict_cov's ldc and gp2d_gemm's ldc (outputs are stored per element).
+ * gp2d_dfact_zpart / gp2d_dfact_alpha_blocks read W per element but keep the distributed factor's
+ * check (ldw even): they take the matrix the other gp2d_dfact_* entries wrote.  A batched entry's
+ * problem stride sA must be even as well.  gp2d_dfact_*'s panel and the packed payload of
+ * gp2d_pack_lower / gp2d_ozaki_prepare_packed are GEMM / pair-copy operands too: 16-byte aligned.  Every entry checks its rule on the
+ * host before any device work and names the parameter in gp2d_last_error().
  */
 #ifndef GP2D_H
 #define GP2D_H
@@ -145,7 +163,7 @@ int gp2d_potrf_inv(double* A, int64_t n, int64_t lda, double* dinv, int* info_de
 
 /* gp2d_potrf_batched / gp2d_trtri_batched: nprob independent fits of one size in one
  * chain — problem q's SPD matrix at A + q·sA (sA ≥ n·lda elements), its diagonal-block
- * inverses at dinv + q·n·128, its info word at info_dev[q].  Each launch carries every
+ * inverses at dinv + q·n·128 (sA even), its info word at info_dev[q].  Each launch carries every
  * problem, so a sweep's settings (runKrig.py:14-17's hyperparameter table) or a job
  * stream's next fits pay the latency-bound diagonal chain once.  Problem q's results are
  * bit for bit those of gp2d_potrf / gp2d_trtri on it alone.  nprob ≤ 64.             */
@@ -281,6 +299,7 @@ int gp2d_predict_cov(const double* W, int64_t n, int64_t ldw, const double* alph
  * gp2d_ozaki_prepare: once per fit, W → residue planes wres (≤ gp2d_ozaki_wres_bytes(n)
  * bytes) and per-row scales rowscale (n doubles); *nmod_out receives the number of moduli
  * the data needs (from per-row L1 bounds of the scaled W; synchronises the stream once).
+ * ldw >= n and even: 0 is not a leading dimension (the packed layout has its own entry below).
  * wbits / kbits: integer bits per scaled W row, 0 (the default, 49) or 49..60, and of the scaled
  * K*, 0 (45) or 45..50 — the accuracy guard's choice (gp2d_ozaki_guard_bits; more bits cost about
  * one modulus per 8).  The row scales carry wbits; every later call that makes or reads K* planes
@@ -485,7 +504,7 @@ int gp2d_cv_groups(const double* W, int64_t n, int64_t ldw, const double* alpha,
 /* ---- dense helpers (the GP_scripts functional API on explicit matrices) ------------
  * gp2d_gemm: C = alpha·A·op(B) + beta·C on the FP64 MFMA GEMM core; op(B) = B (transb = 0,
  *   B is k×n) or Bᵀ (transb = 1, B is n×k); row-major; m, n multiples of 128, k of 16 (the
- *   Python layer pads).  Replaces the np.dot chains of GP_scripts.getMean (GP_scripts.py:44-46)
+ *   Python layer pads); lda, ldb even with A, B 16-byte aligned, ldc any; beta = 0 does not read C.  Replaces the np.dot chains of GP_scripts.getMean (GP_scripts.py:44-46)
  *   and getCov (GP_scripts.py:48-54, Ks·Ki·Ksᵀ).
  * gp2d_transpose: At = Aᵀ for an n×n matrix (n a multiple of 64, At with leading dim n).
  *   Forms K⁻¹ = WᵀW from W = L⁻¹ in place of np.linalg.inv (GP_scripts.py:50).           */

@@ -185,6 +185,66 @@ int main() {
   EXPECT_ERR(gp2d_gemm(2, 4, 4, 4, 1.0, buf, 4, buf, 4, 0.0, buf, 4, nullptr));
   EXPECT_ERR(gp2d_gemm(0, 4, 4, 4, 1.0, buf, 3, buf, 4, 0.0, buf, 4, nullptr));
   EXPECT_ERR(gp2d_transpose(buf, 100, 100, buf, nullptr));
+  // ---- leading dimensions (include/gp2d.h "Leading dimensions"): below the row length everywhere;
+  // odd where 16-byte pairs are moved; 0 (the packed layout's marker) for gp2d_ozaki_prepare
+  const size_t big = (size_t)1 << 40;
+  int64_t gs[2] = {0, 1};
+  EXPECT_ERR(gp2d_assemble_cols(buf, 1, 64, &df, 0.0, buf, 127, 0, 64, nullptr));
+  EXPECT_ERR(gp2d_potrf_inv(buf, 256, 254, buf, &info, buf, big, nullptr));
+  EXPECT_ERR(gp2d_potrf_inv(buf, 256, 257, buf, &info, buf, big, nullptr));
+  EXPECT_ERR(gp2d_trtri(buf, 256, 254, nullptr, buf, big, nullptr));
+  EXPECT_ERR(gp2d_trtri(buf, 256, 257, nullptr, buf, big, nullptr));
+  EXPECT_ERR(gp2d_potrf_batched(buf, 256, 254, 256 * 300, 2, buf, &info, nullptr));
+  EXPECT_ERR(gp2d_potrf_batched(buf, 256, 257, 256 * 300, 2, buf, &info, nullptr));
+  EXPECT_ERR(gp2d_potrf_batched(buf, 256, 256, 256 * 256 + 1, 2, buf, &info, nullptr));          // sA odd
+  EXPECT_ERR(gp2d_trtri_batched(buf, 256, 254, 256 * 300, 2, buf, buf, big, nullptr));
+  EXPECT_ERR(gp2d_trtri_batched(buf, 256, 257, 256 * 300, 2, buf, buf, big, nullptr));
+  EXPECT_ERR(gp2d_trtri_batched(buf, 256, 256, 256 * 256 + 1, 2, buf, buf, big, nullptr));       // sA odd
+  EXPECT_ERR(gp2d_potrs_inv(buf, 256, 255, buf, buf, buf, big, nullptr));
+  EXPECT_ERR(gp2d_predict(buf, 256, 254, buf, buf, 100, 128, buf, 10, &df, 0, 0.0, 1, buf, buf, 128, buf, big, nullptr));
+  EXPECT_ERR(gp2d_predict(buf, 256, 257, buf, buf, 100, 128, buf, 10, &df, 0, 0.0, 1, buf, buf, 128, buf, big, nullptr));
+  EXPECT_ERR(gp2d_predict_field(buf, 256, 254, buf, buf, 100, 128, buf, 10, &mixed, GP2D_FIELD_VORTICITY, 1, buf, buf, 128, buf, big, nullptr));
+  EXPECT_ERR(gp2d_predict_field(buf, 256, 257, buf, buf, 100, 128, buf, 10, &mixed, GP2D_FIELD_VORTICITY, 1, buf, buf, 128, buf, big, nullptr));
+  EXPECT_ERR(gp2d_predict_grad(buf, 256, 254, buf, buf, 100, 128, buf, 10, &mixed, 1, buf, buf, 128, buf, big, nullptr));
+  EXPECT_ERR(gp2d_predict_grad(buf, 256, 257, buf, buf, 100, 128, buf, 10, &mixed, 1, buf, buf, 128, buf, big, nullptr));
+  EXPECT_ERR(gp2d_predict_cov(buf, 256, 254, buf, buf, 100, 128, buf, 10, &mixed, 0.0, buf, buf, 128, buf, big, nullptr));
+  EXPECT_ERR(gp2d_predict_cov(buf, 256, 257, buf, buf, 100, 128, buf, 10, &mixed, 0.0, buf, buf, 128, buf, big, nullptr));
+  EXPECT_ERR(gp2d_predict_cov(buf, 256, 256, buf, buf, 100, 128, buf, 10, &mixed, 0.0, buf, buf, 127, buf, big, nullptr));   // ldc < q
+  EXPECT_ERR(gp2d_ozaki_prepare(buf, 256, 254, &df, 0, 0, wb, buf, &nmod, nullptr));
+  EXPECT_ERR(gp2d_ozaki_prepare(buf, 256, 257, &df, 0, 0, wb, buf, &nmod, nullptr));
+  EXPECT_ERR(gp2d_ozaki_prepare(buf, 256, 0, &df, 0, 0, wb, buf, &nmod, nullptr));               // not the packed layout
+  EXPECT_ERR(gp2d_ozaki_prepare_async(buf, 256, 254, &df, 0.0025, 0, 0, wb, buf, &nmod, nullptr));
+  EXPECT_ERR(gp2d_ozaki_prepare_async(buf, 256, 257, &df, 0.0025, 0, 0, wb, buf, &nmod, nullptr));
+  EXPECT_ERR(gp2d_ozaki_guard(buf, 256, 255, 100, 128, 0.0025, buf, buf, big, nullptr));
+  EXPECT_ERR(gp2d_lml(buf, 256, 255, buf, buf, 200, buf, nullptr));
+  EXPECT_ERR(gp2d_lml_grad(buf, 256, 254, buf, buf, 100, 128, &df, buf, buf, big, nullptr));
+  EXPECT_ERR(gp2d_lml_grad(buf, 256, 257, buf, buf, 100, 128, &df, buf, buf, big, nullptr));
+  EXPECT_ERR(gp2d_cv_points(buf, 256, 255, buf, buf, 100, 128, 2, nullptr, buf, buf, buf, buf, buf, buf, big, nullptr));
+  EXPECT_ERR(gp2d_cv_groups(buf, 256, 255, buf, buf, 100, 128, 2, gs, ib, 1, nullptr, buf, buf, buf, &info, buf, big, nullptr));
+  EXPECT_ERR(gp2d_gemm(0, 128, 128, 16, 1.0, buf, 14, buf, 128, 0.0, buf, 128, nullptr));        // lda < k
+  EXPECT_ERR(gp2d_gemm(0, 128, 128, 16, 1.0, buf, 17, buf, 128, 0.0, buf, 128, nullptr));        // lda odd
+  EXPECT_ERR(gp2d_gemm(0, 128, 128, 16, 1.0, buf, 16, buf, 126, 0.0, buf, 128, nullptr));        // ldb < n
+  EXPECT_ERR(gp2d_gemm(0, 128, 128, 16, 1.0, buf, 16, buf, 129, 0.0, buf, 128, nullptr));        // ldb odd
+  EXPECT_ERR(gp2d_gemm(1, 128, 128, 16, 1.0, buf, 16, buf, 14, 0.0, buf, 128, nullptr));         // ldb < k (transb)
+  EXPECT_ERR(gp2d_gemm(0, 128, 128, 16, 1.0, buf, 16, buf, 128, 0.0, buf, 127, nullptr));        // ldc < n
+  EXPECT_ERR(gp2d_transpose(buf, 64, 63, buf2, nullptr));
+  EXPECT_ERR(gp2d_dfact_panel(buf, 1024, 1022, 0, buf, &info, buf, big, nullptr));
+  EXPECT_ERR(gp2d_dfact_panel(buf, 1024, 1025, 0, buf, &info, buf, big, nullptr));
+  EXPECT_ERR(gp2d_dfact_update(buf, 1024, 1025, 0, buf, 1, 0, 0, 2, nullptr));
+  EXPECT_ERR(gp2d_dfact_invstep(buf, 1024, 1025, 0, buf, 1, 0, buf, big, nullptr));
+  EXPECT_ERR(gp2d_dfact_zpart(buf, 1024, 1022, 0, 1, 1, buf, buf, nullptr));
+  EXPECT_ERR(gp2d_dfact_zpart(buf, 1024, 1025, 0, 1, 1, buf, buf, nullptr));
+  EXPECT_ERR(gp2d_dfact_alpha_blocks(buf, 1024, 1022, 0, 1, 1, buf, buf, buf, big, nullptr));
+  EXPECT_ERR(gp2d_dfact_alpha_blocks(buf, 1024, 1025, 0, 1, 1, buf, buf, buf, big, nullptr));
+  EXPECT_ERR(gp2d_zero_upper(buf, 256, 254, nullptr));
+  EXPECT_ERR(gp2d_zero_upper(buf, 256, 257, nullptr));
+  EXPECT_ERR(gp2d_pack_lower(buf, 256, 254, buf2, 0, nullptr));
+  EXPECT_ERR(gp2d_pack_lower(buf, 256, 257, buf2, 0, nullptr));
+  // the base of a matrix moved in 16-byte pairs must be 16-byte aligned
+  double* odd8 = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(buf) & ~(uintptr_t)15) + 8);
+  EXPECT_ERR(gp2d_potrf(odd8, 128, 128, buf2, &info, nullptr, 0, nullptr));
+  EXPECT_ERR(gp2d_zero_upper(odd8, 128, 128, nullptr));
+  EXPECT_ERR(gp2d_gemm(0, 128, 128, 16, 1.0, odd8, 16, buf2, 128, 0.0, buf2, 128, nullptr));
   // ---- timing hooks (host state only)
   gp2d_timing_enable(1);
   double ms = -1, fl = -1;

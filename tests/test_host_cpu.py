@@ -663,3 +663,126 @@ def test_job_mode_matches_the_bench_line():
             got = E._job_mode(first, "ozaki", True, fa, bf, ba)
             assert got == (want["fits_ahead"], want["batch_fits"], want["batch_ahead"]), (ntrain, m, fa, bf, ba)
     assert E._job_mode(first, "ozaki", True, None, None, None) == (1, 1, False)
+
+
+# ------------------------------------------------------------------ the leading-dimension contract
+def header_prototypes():
+    """{function: [parameter names]} of every prototype in include/gp2d.h."""
+    txt = open(os.path.join(ROOT, "include", "gp2d.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    protos = {}
+    for name, params in re.findall(r"\b(gp2d_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt):
+        names = []
+        for p in params.split(","):
+            ids = re.findall(r"[A-Za-z_]\w*", re.sub(r"\[[^\]]*\]", "", p))
+            if ids and ids != ["void"]:
+                names.append(ids[-1])
+        protos[name] = names
+    return protos
+
+
+LD_NAMES = ("ld", "lda", "ldb", "ldc", "ldw")
+# Per entry: the other arguments of a call that is valid but for its leading dimension, and per
+# leading dimension (row length, needs_even).  needs_even is what include/gp2d.h's "Leading
+# dimensions" paragraph states: True where a kernel moves the matrix in 16-byte pairs (the base
+# must then be 16-byte aligned too), False where every access is one double.
+_FIT = dict(n=256, ntr=100, ntr_pad=128, npad=128, m=10, chunk=128, work_bytes=1 << 40)
+_DF = dict(n=1024, s=0, nranks=1, rank=0, t_lo=0, t_hi=2, t0=0, dt=1, count=1, work_bytes=1 << 40)
+LD_TABLE = {
+    "gp2d_assemble": (dict(na=1, na_pad=64, nb=1, nb_pad=64), {"ld": (128, False)}),
+    "gp2d_assemble_cols": (dict(n=1, n_pad=64, c0=0, ncols=64), {"ld": (128, False)}),
+    "gp2d_potrf": (dict(n=256), {"lda": (256, True)}),
+    "gp2d_trtri": (dict(n=256, work_bytes=1 << 40), {"lda": (256, True)}),
+    "gp2d_potrf_inv": (dict(n=256, work_bytes=1 << 40), {"lda": (256, True)}),
+    "gp2d_potrf_batched": (dict(n=256, sA=256 * 300, nprob=2), {"lda": (256, True)}),
+    "gp2d_trtri_batched": (dict(n=256, sA=256 * 300, nprob=2, work_bytes=1 << 40), {"lda": (256, True)}),
+    "gp2d_potrs_inv": (dict(n=256, work_bytes=1 << 40), {"ldw": (256, False)}),
+    "gp2d_predict": (dict(_FIT, compute_var=1), {"ldw": (256, True)}),
+    "gp2d_predict_field": (dict(_FIT, field=1, compute_var=1), {"ldw": (256, True)}),
+    "gp2d_predict_grad": (dict(_FIT, compute_cov=1), {"ldw": (256, True)}),
+    "gp2d_predict_cov": (dict(_FIT), {"ldw": (256, True), "ldc": (128, False)}),
+    "gp2d_ozaki_prepare": (dict(n=256), {"ldw": (256, True)}),
+    "gp2d_ozaki_prepare_async": (dict(n=256, diag_add=0.0025), {"ldw": (256, True)}),
+    "gp2d_ozaki_guard": (dict(_FIT, diag_add=0.0025), {"ldw": (256, False)}),
+    "gp2d_lml": (dict(n=256, nobs=200), {"ldw": (256, False)}),
+    "gp2d_lml_grad": (dict(_FIT), {"ldw": (256, True)}),
+    "gp2d_kernel_grad": (dict(na=10, nb=10, work_bytes=1 << 40), {"ld": (20, False)}),
+    "gp2d_cv_points": (dict(_FIT, bd=2), {"ldw": (256, False)}),
+    "gp2d_cv_groups": (dict(_FIT, bd=2, ngroups=1), {"ldw": (256, False)}),
+    "gp2d_gemm": (dict(transb=0, m=128, n=128, k=16, alpha=1.0), {"lda": (16, True), "ldb": (128, True),
+                                                                  "ldc": (128, False)}),
+    "gp2d_transpose": (dict(n=64), {"lda": (64, False)}),
+    "gp2d_dfact_panel": (_DF, {"lda": (1024, True)}),
+    "gp2d_dfact_update": (_DF, {"lda": (1024, True)}),
+    "gp2d_dfact_invstep": (_DF, {"lda": (1024, True)}),
+    "gp2d_dfact_zpart": (_DF, {"ldw": (1024, True)}),
+    "gp2d_dfact_alpha_blocks": (_DF, {"ldw": (1024, True)}),
+    "gp2d_zero_upper": (dict(n=256), {"lda": (256, True)}),
+    "gp2d_pack_lower": (dict(n=256), {"ldw": (256, True)}),
+}
+# entries whose even rule comes from a shared check although they read per element: no base rule
+LD_NO_BASE_RULE = {"gp2d_dfact_zpart", "gp2d_dfact_alpha_blocks"}
+
+
+def _ld_call(name, values, ptr=1):
+    """Call entry `name` with `values` by parameter name; every other pointer is `ptr` (never
+    dereferenced: the call is refused on the host), every other number 0."""
+    import ctypes
+    from gp2d import _native as N
+    L = N.lib()
+    params = header_prototypes()[name]
+    _, argtypes = N._SIGS[name]
+    assert len(params) == len(argtypes), name
+    keep = []
+    args = []
+    for p, t in zip(params, argtypes):
+        if p == "stream":
+            args.append(None)
+        elif p == "gstart":
+            keep.append((ctypes.c_int64 * 2)(0, 1))
+            args.append(ctypes.cast(keep[-1], ctypes.c_void_p))
+        elif t is N._KP:
+            keep.append(N.vector_kernel_desc(N.KIND_MIXED, 5.0, 4.0, 0.5))
+            args.append(ctypes.byref(keep[-1]))
+        elif t is ctypes.c_void_p:
+            args.append(ctypes.c_void_p(ptr))
+        elif t in (ctypes.c_int64, ctypes.c_int, ctypes.c_size_t):
+            args.append(int(values.get(p, 0)))
+        elif t is ctypes.c_double:
+            args.append(float(values.get(p, 0.0)))
+        else:   # int* out-parameters
+            keep.append(ctypes.c_int(0))
+            args.append(ctypes.byref(keep[-1]))
+    rc = getattr(L, name)(*args)
+    return rc, L.gp2d_last_error().decode()
+
+
+def test_leading_dimension_table_covers_the_header():
+    """An entry that gains a leading dimension must be added to LD_TABLE: the functions of gp2d.h
+    with a parameter named ld, lda, ldb, ldc or ldw, and those parameters, are exactly the table's."""
+    want = {f: {p for p in ps if p in LD_NAMES} for f, ps in header_prototypes().items()}
+    want = {f: ps for f, ps in want.items() if ps}
+    assert len(want) >= 26
+    assert set(want) == set(LD_TABLE)
+    for f, ps in want.items():
+        assert ps == set(LD_TABLE[f][1]), f
+
+
+@pytest.mark.parametrize("name", sorted(LD_TABLE))
+def test_leading_dimension_contract_is_enforced(name):
+    """Every entry refuses, on the host and with a message naming the parameter, a leading
+    dimension below the row length, the smallest forbidden alignment (odd where 16-byte pairs are
+    moved; 0, the packed layout's marker, for gp2d_ozaki_prepare) and, where the rule is even, a
+    base pointer that is only 8-byte aligned."""
+    others, lds = LD_TABLE[name]
+    base = dict(others, **{p: row for p, (row, _) in lds.items()})
+    for p, (row, even) in lds.items():
+        bad = [row - 1, row - 2] + ([row + 1] if even else []) + ([0] if name == "gp2d_ozaki_prepare" else [])
+        for v in bad:
+            rc, msg = _ld_call(name, dict(base, **{p: v}))
+            assert rc < 0 and re.search(rf"\b{p}\b", msg), (name, p, v, rc, msg)
+            if even and v == row + 1:
+                assert "even" in msg, (name, p, msg)
+    if any(even for _, even in lds.values()) and name not in LD_NO_BASE_RULE:
+        rc, msg = _ld_call(name, base, ptr=8)
+        assert rc < 0 and "16-byte aligned" in msg, (name, rc, msg)
