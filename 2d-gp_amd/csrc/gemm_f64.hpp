@@ -12,39 +12,159 @@
 //     and solve_triangular+einsum (_gpr.py:454-475).
 //   * the gradient predict's V = L⁻¹·Cᵀ with the 4 × 4 Gram per target fused in the epilogue
 //     (NN, a_lower, EPI_COLGRAM; grad.hpp)
+//   * K_y⁻¹ = WᵀW of the LML gradient             (TN, a_upper, c_lower)
+//   * the joint posterior covariance's VᵀV (postcov.hpp: its own kernel around tile_product)
 //
 // MFMA f64 lane maps (verified on MI355X, tools/microbench/f64_rates.hip):
 //   A: lane l holds A[l&15][l>>4]; B: lane l holds B[l>>4][l&15];
 //   C/D: acc[r] of lane l is C[(l>>4) + 4r][l&15].
-// LDS images: A as [BM][BK+2] and Bᵀ-stored B as [BN][BK+2] (stride ≡ 2 mod 32
-// doubles: a 32-lane half reads 16 rows × 2 k-columns conflict-free); NN B as
-// [BK][BN+16] (stride ≡ 16 mod 32: 2 rows × 16 columns conflict-free).
+// The K loop is written once (tile_product) over two operand images, KContigImage and
+// KMajorImage below; a product is named by op(A), op(B): NN and NT read A K-contiguous, TN reads
+// it K-major (A stored K×M, no transposed copy).
 // Problem sizes are multiples of 128 (the engine pads), so there are no edge tiles.
 #pragma once
+#include <type_traits>
 #include "common.hpp"
 
 namespace gp2d {
 
 constexpr int GBM = 128, GBN = 128, GBK = 16;
-constexpr int AS = GBK + 2;
-constexpr int BS_NN = GBN + 16;
-constexpr int BS_NT = GBK + 2;
-constexpr int A_TILE = GBM * AS;                                            // 2304
-constexpr int B_TILE = (GBK * BS_NN > GBN * BS_NT) ? GBK * BS_NN : GBN * BS_NT;  // 2304
-constexpr int STAGE = A_TILE + B_TILE;
+
+// An operand image: how a 128 (tile) × 16 (k) slab of one operand lies in LDS, which 16-byte
+// piece of it each of the 256 threads prefetches from global memory (four per thread and slab),
+// where that piece is stored, and where the MFMA fragment element (t, k) is read.  M is the
+// operand's base, ld its leading dimension, t0 the tile origin, k0 the slab's first k.
+//
+// K-contiguous: the operand is stored tile-index-major (A of NN / NT: M×K; B of NT: N×K).  LDS
+// [128][GBK + 2]; a pass covers 32 rows × 16 k.  A 32-lane half of the fragment ds_read_b64 reads
+// 16 rows × 2 k-columns; the row stride is 18 doubles ≡ 2 (mod 32), so the half covers all 64
+// banks once — conflict-free.
+struct KContigImage {
+  static constexpr int LD = GBK + 2, SIZE = 128 * LD;   // 2304 doubles
+  static __device__ __forceinline__ void gload(d2 (&r)[4], const double* __restrict__ M, int64_t ld, int t0, int k0) {
+    const int tr = threadIdx.x >> 3, kc = (threadIdx.x & 7) * 2;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) r[q] = *reinterpret_cast<const d2*>(M + (int64_t)(t0 + tr + 32 * q) * ld + k0 + kc);
+  }
+  static __device__ __forceinline__ void swrite(double* S, const d2 (&r)[4]) {
+    const int tr = threadIdx.x >> 3, kc = (threadIdx.x & 7) * 2;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) *reinterpret_cast<d2*>(S + (tr + 32 * q) * LD + kc) = r[q];
+  }
+  static __device__ __forceinline__ double frag(const double* S, int t, int k) { return S[t * LD + k]; }
+};
+
+// K-major: the operand is stored k-major (B of NN / TN: K×N; A of TN: K×M).  LDS [GBK][128 + 16];
+// a pass covers 4 k-rows × 128 columns.  Lane l of a wave reads element (kk + (l>>4))·LD + c +
+// (l&15): a 32-lane half of the ds_read_b64 reads 2 rows × 16 consecutive doubles; a row is 32
+// consecutive dwords and the row stride 288 dwords ≡ 32 (mod 64), so the half covers all 64
+// banks once — conflict-free, for an A operand as for a B operand.
+struct KMajorImage {
+  static constexpr int LD = 128 + 16, SIZE = GBK * LD;   // 2304 doubles
+  static __device__ __forceinline__ void gload(d2 (&r)[4], const double* __restrict__ M, int64_t ld, int t0, int k0) {
+    const int kr = threadIdx.x >> 6, tc = (threadIdx.x & 63) * 2;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) r[q] = *reinterpret_cast<const d2*>(M + (int64_t)(k0 + kr + 4 * q) * ld + t0 + tc);
+  }
+  static __device__ __forceinline__ void swrite(double* S, const d2 (&r)[4]) {
+    const int kr = threadIdx.x >> 6, tc = (threadIdx.x & 63) * 2;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) *reinterpret_cast<d2*>(S + (kr + 4 * q) * LD + tc) = r[q];
+  }
+  static __device__ __forceinline__ double frag(const double* S, int t, int k) { return S[k * LD + t]; }
+};
+
+// LDS of one tile product, in doubles: two ring buffers of an A image and a B image (73,728 bytes).
+constexpr int TILE_LDS = 2 * (KContigImage::SIZE + KMajorImage::SIZE);
+static_assert(KContigImage::SIZE == KMajorImage::SIZE, "either image fits either half of a ring buffer");
+
+// acc[mi][ni][r] of this thread is the tile product's element (row(mi, r), col(ni)), for the tile
+// at (i0, j0): wave (wr, wc) of the 2×2 owns a 64×64 sub-tile, lane (lr, lk) = (l & 15, l >> 4).
+struct AccMap {
+  int r0, c0;
+  __device__ __forceinline__ AccMap(int i0, int j0) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    r0 = i0 + (wid >> 1) * 64 + (lane >> 4);
+    c0 = j0 + (wid & 1) * 64 + (lane & 15);
+  }
+  __device__ __forceinline__ int row(int mi, int r) const { return r0 + mi * 16 + 4 * r; }
+  __device__ __forceinline__ int col(int ni) const { return c0 + ni * 16; }
+};
+
+// The 128×128 tile product acc = op(A)[i0.., kb..ke) · op(B)[kb..ke), j0..) of a 256-thread
+// workgroup, k ascending in GBK slabs through the double-buffered LDS ring `smem` (TILE_LDS
+// doubles): slab k+1 is fetched into registers before the MFMAs of slab k and stored to the other
+// buffer after them, one barrier per slab.  One fixed order, no atomics: reproducible bit for bit.
+// b_is_a: op(B)'s panel is op(A)'s (same image, same matrix, i0 == j0 — a diagonal tile of VᵀV);
+// one panel is loaded and staged, and both fragments are read from it.
+template <class AImg, class BImg>
+__device__ __forceinline__ void tile_product(d4 (&acc)[4][4], const double* __restrict__ A, int64_t lda, int i0,
+                                             const double* __restrict__ B, int64_t ldb, int j0, int kb, int ke,
+                                             double* smem, bool b_is_a) {
+  constexpr int STAGE = AImg::SIZE + BImg::SIZE;
+  static_assert(2 * STAGE == TILE_LDS, "the ring holds two stages");
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wr = wid >> 1, wc = wid & 1;
+  const int lr = lane & 15, lk = lane >> 4;
+
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = d4{0.0, 0.0, 0.0, 0.0};
+  if (kb >= ke) return;
+
+  d2 ra[4], rb[4];
+  auto gload = [&](int k0) {
+    AImg::gload(ra, A, lda, i0, k0);
+    if (!b_is_a) BImg::gload(rb, B, ldb, j0, k0);
+  };
+  auto swrite = [&](int buf) {
+    double* As = smem + buf * STAGE;
+    AImg::swrite(As, ra);
+    if (!b_is_a) BImg::swrite(As + AImg::SIZE, rb);
+  };
+
+  gload(kb);
+  swrite(0);
+  __syncthreads();
+  int buf = 0;
+  for (int k0 = kb; k0 < ke; k0 += GBK) {
+    const bool has_next = (k0 + GBK) < ke;
+    if (has_next) gload(k0 + GBK);
+    const double* As = smem + buf * STAGE;
+    const double* Bs = b_is_a ? As : As + AImg::SIZE;
+#pragma unroll
+    for (int kk = 0; kk < GBK; kk += 4) {
+      double a[4], b[4];
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) a[mi] = AImg::frag(As, wr * 64 + mi * 16 + lr, kk + lk);
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) b[ni] = BImg::frag(Bs, wc * 64 + ni * 16 + lr, kk + lk);
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+    }
+    if (has_next) swrite(buf ^ 1);
+    __syncthreads();
+    buf ^= 1;
+  }
+}
 
 enum { EPI_STORE = 0, EPI_COLSQ = 1, EPI_COLGRAM = 2 };
 constexpr int EPI_COLGRAM_PAIRS = 10;   // entries (a ≤ b) of a 4 × 4 Gram
 
 struct GemmParams {
-  const double* A; int64_t lda; int64_t sA;   // M×K row-major
+  const double* A; int64_t lda; int64_t sA;   // M×K row-major; TN (K-major A): K×M row-major, lda ≥ M
   const double* B; int64_t ldb; int64_t sB;   // NN: K×N row-major; NT: N×K row-major
   double* C; int64_t ldc; int64_t sC;         // M×N
   int M, N, K;
   double alpha, beta;
-  int a_lower;   // A lower-triangular: row block i0 only needs k < i0+BM
+  // a_lower / a_upper describe op(A), the M×K factor of the product, whichever way A is stored
+  int a_lower;   // op(A) lower-triangular: row block i0 only needs k < i0+BM
   int b_lower;   // (NN) B lower-triangular: column block j0 only needs k >= j0
-  int a_upper;   // A upper-triangular: row block i0 only needs k >= i0
+  int a_upper;   // op(A) upper-triangular: row block i0 only needs k >= i0 (TN: the stored A is lower)
   int c_lower;   // enumerate lower tiles of a square C; diagonal tiles store i >= j
   int rev_rows;  // dispatch heavy (large i0) row blocks first (a_lower)
   int xcd_cols;  // 1-D grid: groups of 8 column tiles × all row blocks, column tile = XCD label
@@ -86,9 +206,11 @@ __device__ __forceinline__ void tri_tile(int t, int& bi, int& bj) {
   bj = t - r * (r + 1) / 2;
 }
 
-template <bool BT, int EPI>
+// op(B) = Bᵀ with BT, op(A) = Aᵀ with AT (TN; EPI_STORE only).
+template <bool BT, int EPI, bool AT = false>
 __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams p) {
-  __shared__ double smem[2 * STAGE];
+  static_assert(!(AT && BT) && (!AT || EPI == EPI_STORE), "TN is built for the STORE epilogue; there is no TT");
+  __shared__ double smem[TILE_LDS];
 
   int bi, bj;
   if (p.c_lower) {
@@ -135,84 +257,18 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wr = wid >> 1, wc = wid & 1;
-  const int lr = lane & 15, lk = lane >> 4;
 
   d4 acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = d4{0.0, 0.0, 0.0, 0.0};
-
-  // global -> register prefetch mapping
-  const int ar = tid >> 3, ac = (tid & 7) * 2;      // A / Bᵀ: 32 rows × 16 cols per pass
-  const int br = tid >> 6, bc = (tid & 63) * 2;     // NN B:   4 rows × 128 cols per pass
-  d2 ra[4], rb[4];
-
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      ra[q] = *reinterpret_cast<const d2*>(A + (int64_t)(i0 + ar + 32 * q) * p.lda + k0 + ac);
-    if (BT) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        rb[q] = *reinterpret_cast<const d2*>(B + (int64_t)(j0 + ar + 32 * q) * p.ldb + k0 + ac);
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        rb[q] = *reinterpret_cast<const d2*>(B + (int64_t)(k0 + br + 4 * q) * p.ldb + j0 + bc);
-    }
-  };
-  auto swrite = [&](int buf) {
-    double* As = smem + buf * STAGE;
-    double* Bs = As + A_TILE;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) *reinterpret_cast<d2*>(As + (ar + 32 * q) * AS + ac) = ra[q];
-    if (BT) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) *reinterpret_cast<d2*>(Bs + (ar + 32 * q) * BS_NT + ac) = rb[q];
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) *reinterpret_cast<d2*>(Bs + (br + 4 * q) * BS_NN + bc) = rb[q];
-    }
-  };
-
-  if (kb < ke) {
-    gload(kb);
-    swrite(0);
-    __syncthreads();
-    int buf = 0;
-    for (int k0 = kb; k0 < ke; k0 += GBK) {
-      const bool has_next = (k0 + GBK) < ke;
-      if (has_next) gload(k0 + GBK);
-      const double* As = smem + buf * STAGE;
-      const double* Bs = As + A_TILE;
-#pragma unroll
-      for (int kk = 0; kk < GBK; kk += 4) {
-        double a[4], b[4];
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) a[mi] = As[(wr * 64 + mi * 16 + lr) * AS + kk + lk];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-          if (BT) b[ni] = Bs[(wc * 64 + ni * 16 + lr) * BS_NT + kk + lk];
-          else    b[ni] = Bs[(kk + lk) * BS_NN + wc * 64 + ni * 16 + lr];
-        }
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-      }
-      if (has_next) swrite(buf ^ 1);
-      __syncthreads();
-      buf ^= 1;
-    }
-  }
+  using AImg = std::conditional_t<AT, KMajorImage, KContigImage>;
+  using BImg = std::conditional_t<BT, KContigImage, KMajorImage>;
+  tile_product<AImg, BImg>(acc, A, p.lda, i0, B, p.ldb, j0, kb, ke, smem, false);
 
   if (EPI == EPI_STORE) {
     double* __restrict__ C = khigh ? p.C2 + z * p.sC2 + zq * p.pC2 : p.C + z * p.sC + zq * p.pC;
     const int64_t ldc = khigh ? p.ldc2 : p.ldc;
     const bool diag_tile = (p.c_lower && bi == bj) || (p.cyc_lower && bi + p.mask_off == jt);
     const bool has_beta = p.beta != 0.0;
+    const AccMap at(i0, j0);
     // per 16-row group mi: 16 C loads, then the updates and stores (element-wise load → use →
     // store chains leave one HBM round trip per element).  With β ≠ 0 group mi+1's loads are
     // issued before group mi's updates, so a tile's C read costs one exposed round trip instead
@@ -222,8 +278,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams p) {
       for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = i0 + wr * 64 + mi * 16 + lk + 4 * r;
-          const int col = j0 + wc * 64 + ni * 16 + lr;
+          const int row = at.row(mi, r), col = at.col(ni);
           old[ni][r] = __builtin_nontemporal_load(C + (int64_t)row * ldc + col);
         }
     };
@@ -232,8 +287,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams p) {
       for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = i0 + wr * 64 + mi * 16 + lk + 4 * r;
-          const int col = j0 + wc * 64 + ni * 16 + lr;
+          const int row = at.row(mi, r), col = at.col(ni);
           double v = p.alpha * acc[mi][ni][r];
           if (has_beta) v = fma(p.beta, old[ni][r], v);
           if (!(diag_tile && col - j0 > row - i0)) C[(int64_t)row * ldc + col] = v;
@@ -317,10 +371,14 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams p) {
 }
 
 // Host-side launcher.  Returns 0 / negative error.
-template <bool BT, int EPI>
+template <bool BT, int EPI, bool AT = false>
 inline int launch_gemm(const GemmParams& pin, int batch, hipStream_t s, int nprob = 1) {
   if (pin.M <= 0 || pin.N <= 0 || batch <= 0 || nprob <= 0) return 0;
   GemmParams p = pin;
+  if (AT && (batch != 1 || nprob != 1 || p.ksplit > 0 || p.jgrp > 0 || p.cyc_lower || p.a_lower)) {
+    set_error("gemm: TN runs one unsplit problem, without a_lower or block-cyclic columns");
+    return -2;
+  }
   if (nprob > 1 && EPI != EPI_STORE) {
     set_error("gemm: a problem batch needs EPI_STORE");
     return -2;
@@ -357,7 +415,7 @@ inline int launch_gemm(const GemmParams& pin, int batch, hipStream_t s, int npro
     set_error("gemm: too many batch entries");
     return -2;
   }
-  gemm_f64_kernel<BT, EPI><<<grid, 256, 0, s>>>(p);
+  gemm_f64_kernel<BT, EPI, AT><<<grid, 256, 0, s>>>(p);
   return check_launch("gemm_f64_kernel");
 }
 

@@ -1881,18 +1881,18 @@ int gp2d_lml_grad(const double* W, int64_t n, int64_t ldw, const double* alpha, 
   GP2D_REQUIRE(ld_even(ldw, n), "lml_grad: ldw must be >= n and even");
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_lml_grad_workspace(n), "lml_grad: workspace too small");
   GP2D_REQUIRE(aligned16(W), "lml_grad: W must be 16-byte aligned");
+  // (the two checks above cover both operands of the TN product below: as A and as B, W is read in
+  // 16-byte pieces at W + k·ldw + i0 + 2·j)
   hipStream_t s = S(stream);
-  const auto [Wt, C, partial] = LmlGradWork(n).at(work);
-  // Wt = Wᵀ (upper), C = Wt·W = K_y⁻¹, lower tiles only
-  transpose_kernel<<<dim3((unsigned)(n / 64), (unsigned)(n / 64)), 256, 0, s>>>(W, n, ldw, Wt);
-  GP2D_CHECK(check_launch("transpose_kernel"));
+  const auto [C, partial] = LmlGradWork(n).at(work);
+  // C = WᵀW = K_y⁻¹, lower tiles only: W is read K-major on both sides, op(A) = Wᵀ is upper
   GemmParams p = gemm_params();
-  p.A = Wt; p.lda = n;
+  p.A = W; p.lda = ldw;
   p.B = W; p.ldb = ldw;
   p.C = C; p.ldc = n;
   p.M = (int)n; p.N = (int)n; p.K = (int)n;
   p.a_upper = 1; p.c_lower = 1;
-  GP2D_CHECK((launch_gemm<false, EPI_STORE>(p, 1, s)));
+  GP2D_CHECK((launch_gemm<false, EPI_STORE, true>(p, 1, s)));
   return launch_pair_grad(k, xtr, ntr, xtr, ntr, ntr_pad, TraceWeights{C, n, alpha, ntr_pad}, partial, 0.5, true,
                           grad_dev, s);
 }

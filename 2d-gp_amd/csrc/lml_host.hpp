@@ -14,23 +14,22 @@ constexpr int64_t grad_blocks(int64_t ncols_pad, int64_t nrows) {
 }
 constexpr size_t grad_partial_bytes(int64_t nblk) { return F64 * (size_t)nblk * LML_MAXG; }
 
-// Workspace of gp2d_lml_grad: Wt = Wᵀ (n × n) | C = K_y⁻¹ (n × n) | the partial sums.  The size is a
+// Workspace of gp2d_lml_grad: C = K_y⁻¹ (n × n) | the partial sums.  The size is a
 // function of n = bd·ntr_pad alone, so the partials are sized for one column tile and one row
 // point more than n × n points, which holds the launch's grad_blocks(ntr_pad, ntr) for either bd.
 struct LmlGradWork {
-  size_t Wt = 0, C = 0, partial = 0, total = 0;
+  size_t C = 0, partial = 0, total = 0;
   constexpr explicit LmlGradWork(int64_t n) {
-    C = F64 * (size_t)n * (size_t)n;
-    partial = 2 * C;
+    partial = F64 * (size_t)n * (size_t)n;
     total = partial + grad_partial_bytes(grad_blocks(n + PT_TILE, n + 1));
   }
-  struct Ptrs { double* Wt; double* C; double* partial; };
-  Ptrs at(void* w) const { return {work_at(w, Wt), work_at(w, C), work_at(w, partial)}; }
+  struct Ptrs { double* C; double* partial; };
+  Ptrs at(void* w) const { return {work_at(w, C), work_at(w, partial)}; }
 };
 constexpr bool lml_grad_work_ok(int64_t n) {
   const LmlGradWork w(n);
   const size_t nn = F64 * (size_t)n * (size_t)n;
-  bool ok = regions_ok({w.Wt, w.C, w.partial, w.total}, {nn, nn, grad_partial_bytes((n / 64 + 1) * (n / 16 + 1))});
+  bool ok = regions_ok({w.C, w.partial, w.total}, {nn, grad_partial_bytes((n / 64 + 1) * (n / 16 + 1))});
   for (int bd = 1; bd <= 2; ++bd)   // the fullest launch: ntr = ntr_pad = n / bd
     ok = ok && w.partial + grad_partial_bytes(grad_blocks(n / bd, n / bd)) <= w.total;
   return ok;

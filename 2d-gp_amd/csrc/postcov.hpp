@@ -11,14 +11,11 @@
 // regenerated in its epilogue (the workspace layout of gp2d_predict_cov is in predict_host.hpp).
 //
 // postcov_kernel: one lower 128×128 tile of Σ per 256-thread workgroup (tri_tile, as the c_lower
-// SYRK), 4 waves as 2×2, each wave 4×4 MFMA tiles of v_mfma_f64_16x16x4_f64.  Both operands are
-// K-major: the A fragment A[i][k] = V[k][i0+i] and the B fragment B[k][j] = V[k][j0+j] are read from
-// the same kind of LDS image, gemm_f64.hpp's NN-B image [GBK][GBN+16].  Lane l of a wave reads
-// element (kk + (l>>4))·BS_NN + c + (l&15): within a 32-lane half of the ds_read_b64 that is 2 rows
-// × 16 consecutive doubles; a row is 32 consecutive dwords and the row stride 288 dwords ≡ 32
-// (mod 64), so the half covers all 64 banks once — conflict-free, for A as for B.  K runs in
-// ascending slabs of 16 through double-buffered LDS with register prefetch, one barrier per slab;
-// no atomics, one fixed order, so the result is reproducible bit for bit.
+// SYRK); the product is gemm_f64.hpp's tile_product with both operands K-major: the A fragment
+// A[i][k] = V[k][i0+i] and the B fragment B[k][j] = V[k][j0+j] are read from the same kind of LDS
+// image (KMajorImage, which carries the bank-conflict argument), and a diagonal tile loads and
+// stages one panel for both.  K ascends over all n rows of V in one fixed order, so the result is
+// reproducible bit for bit.
 //
 // Epilogue: element (R, C) of the tile is prior(R, C) − acc, the prior block k(g_i, g_j) from
 // vec_block_st (the assembly's device function), + diag_add where R == C; rows and columns of
@@ -63,92 +60,32 @@ __device__ __forceinline__ double postcov_prior(const PostcovParams& p, int R, i
 }
 
 __global__ __launch_bounds__(256, 2) void postcov_kernel(PostcovParams p) {
-  __shared__ double smem[2 * 2 * GBK * BS_NN];
-  constexpr int PANEL = GBK * BS_NN;
+  __shared__ double smem[TILE_LDS];
 
   int bi, bj;
   tri_tile(blockIdx.x, bi, bj);
   const int i0 = bi * GBM, j0 = bj * GBN;
   const bool diag_tile = bi == bj;   // one panel serves both operands
-  const double* __restrict__ V = p.V;
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wr = wid >> 1, wc = wid & 1;
-  const int lr = lane & 15, lk = lane >> 4;
 
   d4 acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = d4{0.0, 0.0, 0.0, 0.0};
+  tile_product<KMajorImage, KMajorImage>(acc, p.V, p.ldv, i0, p.V, p.ldv, j0, 0, p.n, smem, diag_tile);
 
-  // global -> register prefetch: 4 rows × 128 columns of each panel per pass
-  const int br = tid >> 6, bc = (tid & 63) * 2;
-  d2 ra[4], rb[4];
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-      ra[s] = *reinterpret_cast<const d2*>(V + (int64_t)(k0 + br + 4 * s) * p.ldv + i0 + bc);
-    if (!diag_tile) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-        rb[s] = *reinterpret_cast<const d2*>(V + (int64_t)(k0 + br + 4 * s) * p.ldv + j0 + bc);
-    }
-  };
-  auto swrite = [&](int buf) {
-    double* As = smem + buf * 2 * PANEL;
-    double* Bs = As + PANEL;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) *reinterpret_cast<d2*>(As + (br + 4 * s) * BS_NN + bc) = ra[s];
-    if (!diag_tile) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) *reinterpret_cast<d2*>(Bs + (br + 4 * s) * BS_NN + bc) = rb[s];
-    }
-  };
-
-  gload(0);
-  swrite(0);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = 0; k0 < p.n; k0 += GBK) {
-    const bool has_next = (k0 + GBK) < p.n;
-    if (has_next) gload(k0 + GBK);
-    const double* As = smem + buf * 2 * PANEL;
-    const double* Bs = diag_tile ? As : As + PANEL;
-#pragma unroll
-    for (int kk = 0; kk < GBK; kk += 4) {
-      double a[4], b[4];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) a[mi] = As[(kk + lk) * BS_NN + wr * 64 + mi * 16 + lr];
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) b[ni] = Bs[(kk + lk) * BS_NN + wc * 64 + ni * 16 + lr];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-    }
-    if (has_next) swrite(buf ^ 1);
-    __syncthreads();
-    buf ^= 1;
-  }
-
-  // acc[mi][ni][r] of lane (lr, lk) is element (R, C) = (rb0 + 16·mi + lk + 4r, cb0 + 16·ni + lr)
-  const int rb0 = i0 + wr * 64, cb0 = j0 + wc * 64;
+  const AccMap at(i0, j0);   // acc[mi][ni][r] is element (R, C) = (at.row(mi, r), at.col(ni))
+  const int lk = (threadIdx.x & 63) >> 4;
   double* __restrict__ Cm = p.C;
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
-      const int Cc = cb0 + ni * 16 + lr;
+      const int Cc = at.col(ni);
       double v[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int R = rb0 + mi * 16 + lk + 4 * r;
+        const int R = at.row(mi, r);
         v[r] = postcov_prior(p, R, Cc, p.diag_add) - acc[mi][ni][r];
         if (!diag_tile || Cc <= R) Cm[(int64_t)R * p.ldc + Cc] = v[r];
       }
-      // transpose the 4×4 (lk, r) block: afterwards v[r] is element (rb0 + 16·mi + 4·lk + r, Cc)
+      // transpose the 4×4 (lk, r) block: afterwards v[r] is element (R0 + r, Cc), R0 below
       {
         const bool o = lk & 1;
         const double s0 = __shfl_xor(o ? v[0] : v[1], 16), s1 = __shfl_xor(o ? v[2] : v[3], 16);
@@ -159,7 +96,7 @@ __global__ __launch_bounds__(256, 2) void postcov_kernel(PostcovParams p) {
         const double s0 = __shfl_xor(o ? v[0] : v[2], 32), s1 = __shfl_xor(o ? v[1] : v[3], 32);
         if (o) { v[0] = s0; v[1] = s1; } else { v[2] = s0; v[3] = s1; }
       }
-      const int R0 = rb0 + mi * 16 + 4 * lk;
+      const int R0 = at.row(mi, 0) + 3 * lk;   // row 16·mi + 4·lk of the wave's sub-tile
       double* mrow = Cm + (int64_t)Cc * p.ldc + R0;   // the mirror: row Cc, columns R0..R0+3
       if (!diag_tile) {
         *reinterpret_cast<d4u*>(mrow) = d4u{v[0], v[1], v[2], v[3]};

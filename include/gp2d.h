@@ -432,7 +432,7 @@ int    gp2d_predict_ozaki_planes(const int8_t* wres, const double* rowscale, int
  *   in natural units, θ = vector2d: (l_df, l_cf, ratio, noise) — entries a kind does not
  *   use are 0, KIND_SCALAR's σ is l_df; VECTOR_ST: (l_df, l_cf, ratio, var_t, l_t, noise); ARD, per term t: (var[t], ls[t][0..D)), then noise —
  *   GPy's param_array order (krig.py:459-466).
- *   K_y⁻¹ = WᵀW is formed in the workspace (gp2d_lml_grad_workspace(n) bytes, ≈ 2n² doubles).
+ *   K_y⁻¹ = WᵀW is formed in the workspace (gp2d_lml_grad_workspace(n) bytes, ≈ n² doubles).
  *   The reference's myKernel.update_gradients_full (myKernel.py:59-105) is not the
  *   derivative of its kernel; this is the exact one.                  */
 int    gp2d_lml(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* y,

@@ -170,7 +170,9 @@ def _kernel_grad_stencil(kind, kw, xa, xb, G):
 
 # The pair kernel's block is 16 row points × 64 column points: sizes on a block edge and one point
 # past it, for every family × weights source, at the tolerances of the neighbouring sizes' tests.
-_LML_EDGE_CASES = [("vector", kind, ratio, n) for n in (16, 17, 64, 65)
+# n = 129: three row tiles of K_y⁻¹ = WᵀW (two-component kinds: 1..64, 65..128 and 129..192 points are
+# one, two and three 128-row tiles; tile (1, 0)'s K range starts at 128)
+_LML_EDGE_CASES = [("vector", kind, ratio, n) for n in (16, 17, 64, 65, 129)
                    for kind, ratio in (("df", 1.0), ("cf", 0.0), ("mixed", 0.35), ("scalar", 1.0))]
 _LML_EDGE_CASES += [("ard", "T2", 0.0, 64), ("ard", "T2", 0.0, 65), ("vector_st", "mixed", 0.35, 65)]
 

@@ -422,16 +422,17 @@ def test_hyper_workspace_sizes_are_the_recorded_ones():
     """The hyperparameter path's and the solve's exported workspace sizes (host functions, no device
     needed) against values recorded from the library of commit ac565a4, before the sizes came from
     the layout structs of csrc/lml_host.hpp: callers allocate by them, so a layout change must not
-    move them.  (The structs' internal consistency — order, no overlap, alignment, and that the LML
+    move them.  gp2d_lml_grad_workspace(n) is that recorded value less 8·n² since K_y⁻¹ = WᵀW became
+    a TN product on W itself and the workspace lost its Wᵀ region.  (The structs' internal consistency — order, no overlap, alignment, and that the LML
     gradient's partial region holds its launch's blocks — is a static_assert there.)"""
     from gp2d import _native as N
     L = N.lib()
     recorded = [
         (L.gp2d_lml_grad_workspace, (0,), 72),                      # no rows: one row of partials
-        (L.gp2d_lml_grad_workspace, (128,), 264088),                # 8·(2·128² + 3·9·9)
-        (L.gp2d_lml_grad_workspace, (256,), 1054696),
-        (L.gp2d_lml_grad_workspace, (8192,), 1078506568),
-        (L.gp2d_lml_grad_workspace, (32768,), 17255551048),
+        (L.gp2d_lml_grad_workspace, (128,), 133016),                # 8·(128² + 3·9·9)
+        (L.gp2d_lml_grad_workspace, (256,), 530408),
+        (L.gp2d_lml_grad_workspace, (8192,), 541635656),
+        (L.gp2d_lml_grad_workspace, (32768,), 8665616456),
         (L.gp2d_kernel_grad_workspace, (0, 0), 72),                 # an empty set sizes as one point
         (L.gp2d_kernel_grad_workspace, (1, 1), 72),
         (L.gp2d_kernel_grad_workspace, (16, 64), 72),               # exactly one block

@@ -1,7 +1,7 @@
 """Which fit kernels slow the int8 variance GEMM in a pipelined job stream:
 from a rocprofv3 kernel-trace database of `bench.py`, every `igemm_nt_mod_kernel` launch of the
 timed (pipelined) region is classed by the fit kernels that run beside it — the trailing SYRK
-(`gemm_f64_kernel<true, 0>`), the TRTRI products (`gemm_f64_kernel<false, 0>`), the
+(`gemm_f64_kernel<true, 0, false>`), the TRTRI products (`gemm_f64_kernel<false, 0, false>`), the
 critical-path chain (`potrf_diag_kernel`, `gemm_f64_panel_kernel`) and the rest of the fit
 (assembly, α, int8 preparation) — by the fraction of its duration each class overlaps.
 

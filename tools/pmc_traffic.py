@@ -20,7 +20,7 @@ def per_launch(path, counter, pattern):
 
 def main():
     fetch_csv, write_csv, out = sys.argv[1:4]
-    pat = sys.argv[4] if len(sys.argv) > 4 else "gemm_f64_kernel<false, 1>"
+    pat = sys.argv[4] if len(sys.argv) > 4 else "gemm_f64_kernel<false, 1,"
     n = int(sys.argv[5]) if len(sys.argv) > 5 else 8192
     ncols = int(sys.argv[6]) if len(sys.argv) > 6 else 16384
     f = per_launch(fetch_csv, "FETCH_SIZE", pat)

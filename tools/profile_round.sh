@@ -26,7 +26,7 @@ if [ "$V" = ozaki ]; then
     "$OUT/pmc_traffic_$V.json" > /dev/null
 else
   python3 tools/pmc_traffic.py "$(csv "$OUT/pmc_fetch_$V")" "$(csv "$OUT/pmc_write_$V")" "$OUT/pmc_traffic_$V.json" \
-    "gemm_f64_kernel<false, 1>" > /dev/null
+    "gemm_f64_kernel<false, 1," > /dev/null
 fi
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof_$V" -o run -- \
   python3 bench.py --full --steps 5 --warmup 2 --cpu-baseline 0 --variance "$V" --pmc-json "$OUT/pmc_traffic_$V.json" \
