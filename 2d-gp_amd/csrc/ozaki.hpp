@@ -530,9 +530,15 @@ __device__ __forceinline__ int swz16(int row, int chunk) {
 
 // s_waitcnt vmcnt(P·W) + lgkmcnt(0) + s_barrier: this wave's LDS-DMA pieces of all but the
 // W youngest slabs (P pieces per slab per wave) have landed, then the workgroup syncs.
-template <int P, int W>
+// BARRIER off (a probe build without DMA, IgemmNoProbe below): only the lgkmcnt(0), which the
+// callers count on for their fragment reads.
+template <int P, bool BARRIER = true, int W>
 __device__ __forceinline__ void vmwait_barrier(std::integral_constant<int, W>) {
   static_assert(P * W < 64, "vmcnt field");
+  if constexpr (!BARRIER) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    return;
+  }
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(P * W) : "memory");
 }
 
@@ -589,10 +595,32 @@ struct IgemmZ {
 };
 constexpr int64_t kIgemmZBatchMaxN = 4096;   // predict_ozaki_impl batches the four-product form's moduli up to this n
 
-template <int TBN, int NST>
+// Probe policy: what a measuring build may take out of the kernel (the switches) or read off it
+// (the hooks, called once per wave at the named points).  This one takes out nothing and reads
+// nothing, and it is the only one the library instantiates (gp2d.hip launches <tbn, nst>); the
+// ablation and stamp policies live in tools/microbench/igemm_probes.hpp and nowhere else.
+struct IgemmNoProbe {
+  static constexpr bool kDma = true;       // the LDS-DMA pieces are issued
+  static constexpr bool kBarrier = true;   // the per-slab vmcnt wait and barrier (off: only with kDma off)
+  static constexpr bool kLdsRead = true;   // the fragment reads (off: the MFMAs run on constant registers)
+  static constexpr bool kMfma = true;      // the MFMAs (off: one xor per half keeps the loads live)
+  static constexpr bool kKLoop = true;     // the K loop as a whole (off: bias, epilogue and stores only)
+  __device__ __forceinline__ void tile_start() {}
+  __device__ __forceinline__ void ring_filled() {}    // the first fragment reads are issued
+  template <int VM>                                   // a FULL step, before vmwait_barrier (which waits
+  __device__ __forceinline__ void before_wait() {}    //   for vmcnt(VM)) ...
+  __device__ __forceinline__ void after_barrier() {}  //   ... and after it
+  __device__ __forceinline__ void ring_tail() {}      // the FULL steps are done
+  __device__ __forceinline__ void before_epilogue() {}
+  __device__ __forceinline__ void after_store() {}
+};
+
+template <int TBN, int NST, class Probe = IgemmNoProbe>
 __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_kernel(
     const int8_t* __restrict__ A, const int8_t* __restrict__ B, uint8_t* C, int64_t ldc, int kslabs_i, int modulus,
     const IgemmProd p, const int* __restrict__ slist, const int* __restrict__ scnt, const IgemmZ zb) {
+  Probe probe;
+  probe.tile_start();
   if (gridDim.z > 1) {
     A += blockIdx.z * zb.sA;
     B += blockIdx.z * zb.sB;
@@ -638,6 +666,7 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
       sl = slist + (int64_t)jb * kslabs + c0;
     }
   }
+  if constexpr (!Probe::kKLoop) nsl = 0;
 
   // the accumulators start at a multiple of m above every |Σ_k a·b| ≤ k_cap·128² (centred
   // residues), so the sums leave the MFMAs non-negative and ≡ the true sums (mod m)
@@ -674,6 +703,7 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
     int8_t* As = smem + st * STG;
     int8_t* Bs = As + I_OP;
     const int so = ks * I_OP;
+    if constexpr (!Probe::kDma) return;
 #pragma unroll
     for (int h = 0; h < AP; ++h) lds_dma16(rA, (lds_ptr_t)(As + (wid * AP + h) * 16 * IBK), voA[h], so);
     const bool q = alias && ks < alias_ks;
@@ -688,6 +718,7 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
   const uint32_t lane_b = (uint32_t)(I_OP + (wc * 64 + l16) * IBK + 16 * swz16(jr + l16, lq));
   auto reada = [&](int st, int half, i4v (&a)[4]) {  // A fragments mi = 4·half .. 4·half+3
     const uint32_t ad = lds_base + st * STG + lane_a;
+    if constexpr (!Probe::kLdsRead) return;
     if (half == 0) {
       asm volatile("ds_read_b128 %0, %1 offset:0" : "=v"(a[0]) : "v"(ad) : "memory");
       asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(a[1]) : "v"(ad) : "memory");
@@ -702,12 +733,17 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
   };
   auto readb = [&](int st, i4v (&b)[4]) {
     const uint32_t ad = lds_base + st * STG + lane_b;
+    if constexpr (!Probe::kLdsRead) return;
     asm volatile("ds_read_b128 %0, %1 offset:0" : "=v"(b[0]) : "v"(ad) : "memory");
     asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(b[1]) : "v"(ad) : "memory");
     asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(b[2]) : "v"(ad) : "memory");
     asm volatile("ds_read_b128 %0, %1 offset:3072" : "=v"(b[3]) : "v"(ad) : "memory");
   };
   auto mfmas = [&](int half, const i4v (&a)[4], const i4v (&b)[4]) {
+    if constexpr (!Probe::kMfma) {
+      acc[0][0][0] += a[0][0] ^ b[0][0];
+      return;
+    }
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -724,15 +760,18 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
 #pragma unroll
     for (int q = 0; q < NST - 1; ++q) issue(slab(q), q);
     int knext = slab(NST - 1);
-    vmwait_barrier<PPW>(std::integral_constant<int, NST - 2>{});   // slab 0 landed (nsl ≥ NST − 1)
+    vmwait_barrier<PPW, Probe::kBarrier>(std::integral_constant<int, NST - 2>{});   // slab 0 landed (nsl ≥ NST − 1)
     // Per slab: MFMA half 0 (A rows 0-63 of the wave) → barrier publishing slab s+1 → reads
     // of slab s+1's B and A-half-0 fragments into the other register set → MFMA half 1.
     // Both waves of a workgroup on a SIMD leave the barrier together, so the next slab's first
     // fragments must already be in flight behind half 1's 16 MFMAs rather than be read after it.
     i4v bA[4], a0A[4], bB[4], a0B[4], a1[4];
+    if constexpr (!Probe::kLdsRead)
+      for (int u = 0; u < 4; ++u) bA[u] = a0A[u] = bB[u] = a0B[u] = a1[u] = i4v{lane, u, wid, 1};
     readb(0, bA);
     reada(0, 0, a0A);
     __builtin_amdgcn_sched_barrier(0);
+    probe.ring_filled();
     // Step kinds: FULL steps issue slab s + NST − 1 and publish s+1 leaving the younger
     // NST − 2 slabs in flight; the tail steps issue nothing and leave W = NST−3 .. 0 slabs in
     // flight; the LAST step has no barrier.  The steady-state loop runs only FULL steps,
@@ -753,7 +792,9 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
       mfmas(0, a0, b);
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (w != LAST) {
-        vmwait_barrier<PPW>(w_c);   // publish slab s+1 (lgkmcnt(0) inside: a1 landed)
+        if constexpr (dma) probe.template before_wait<PPW * w>();
+        vmwait_barrier<PPW, Probe::kBarrier>(w_c);   // publish slab s+1 (lgkmcnt(0) inside: a1 landed)
+        if constexpr (dma) probe.after_barrier();
         const int st1 = (s + 1) % NST;
         readb(st1, bn);
         reada(st1, 0, a0n);
@@ -784,6 +825,7 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
       }
     }
     // tail: NST − 1 steps, W = NST−3, ..., 0, then LAST
+    probe.ring_tail();
     if constexpr (NST == 5) {
       step(F_{}, std::integral_constant<int, 2>{}, s, bA, a0A, bB, a0B);
       step(F_{}, std::integral_constant<int, 1>{}, s + 1, bB, a0B, bA, a0A);
@@ -799,6 +841,7 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
+  probe.before_epilogue();
   // Epilogue: residues mod m, packed 4 rows per dword into an LDS image of Cᵀ [col][row]
   // (pitch 272 B), then written out as coalesced 16-B row runs of the column-major residue
   // plane.  Six full-rate VALU operations per residue (ozaki_mod_u32; no v_mul_lo_u32, no
@@ -860,6 +903,7 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
     const i4v v = *reinterpret_cast<const i4v*>(T + cloc * TP + 16 * ch);
     __builtin_nontemporal_store(v, reinterpret_cast<i4v*>(Cc + (int64_t)cloc * ldc + 16 * ch));
   }
+  probe.after_store();
 }
 
 // ------------------------------------------------------------------ accuracy guard statistics
