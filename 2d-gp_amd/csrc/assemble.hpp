@@ -16,6 +16,8 @@
 #include "common.hpp"
 #include "../../include/gp2d.h"
 
+#include <type_traits>
+
 namespace gp2d {
 
 inline bool is_vector_family(const gp2d_kernel_t* k) {
@@ -183,7 +185,9 @@ constexpr int ASM_LOWER = 2;   // `symmetric` mode: K_y's lower triangle only (g
 //                    (Keep::at(r, c)).  StoresAll: nothing skipped, every store kept;
 //   col(j, c, np)    the column of entry c of column point j;
 //   value(a, b, diag, v), padded(diag, v)   the block of a valid pair and of a padded one; diag
-//                    is i == j.
+//                    is i == j;
+//   stage()          optional: called by every thread before the kernel's barrier, for an entry
+//                    that keeps data of its own in LDS (SumEntry).
 // Launch: grid (column points / 64, ⌈na_pad / ASM_ROWS⌉), 256 threads (launch_cross_cov).
 struct KeepAll {
   __device__ __forceinline__ bool at(int, int) const { return true; }
@@ -193,6 +197,13 @@ struct StoresAll {
   __device__ __forceinline__ bool skip(int64_t, int64_t, int64_t) const { return false; }
   __device__ __forceinline__ Keep keep(int64_t, int64_t) const { return {}; }
 };
+
+// An entry that stages data of its own through LDS has stage(), called by every thread before the
+// kernel's barrier (SumEntry).
+template <class Entry, class = void>
+struct entry_stages : std::false_type {};
+template <class Entry>
+struct entry_stages<Entry, std::void_t<decltype(&Entry::stage)>> : std::true_type {};
 
 template <class Entry>
 __global__ __launch_bounds__(256) void cross_cov_kernel(
@@ -213,6 +224,7 @@ __global__ __launch_bounds__(256) void cross_cov_kernel(
       colpts[t] = (g < nb * pdim) ? xb[g] : 0.0;
     }
   }
+  if constexpr (entry_stages<Entry>::value) e.stage();
   __syncthreads();
   const Point3 b = read_point(e.layout(), colpts, lane);
 #pragma unroll 1
@@ -285,6 +297,83 @@ struct VecEntry {
     v[0][0] = dd; v[0][1] = 0.0; v[1][0] = 0.0; v[1][1] = dd;
   }
 };
+
+// ---- A sum of vector kernels (GP2D_FAMILY_VECTOR_SUM, include/gp2d.h): k[0] the header, k[1..T]
+// the terms.
+inline bool is_sum_family(const gp2d_kernel_t* k) { return k->family == GP2D_FAMILY_VECTOR_SUM; }
+inline const gp2d_kernel_t* sum_term(const gp2d_kernel_t* k, int t) { return k + 1 + t; }
+inline double sum_weight(const gp2d_kernel_t* k, int t) { return k->ls[0][t]; }
+
+// The combinator of cross_cov_kernel's entries: Σ_t w_t·(term t's block).  Point layout, column
+// map, skipped rows, kept stores and the padded pair's block are term 0's (every term shares them:
+// one family, one `symmetric` mode); the terms carry no diag_add of their own, it is added once,
+// after the sum, on the block's diagonal.  The first term is formed without an add (w_0·v_0), so a
+// one-term sum of weight 1 gives its term's bits.
+// The entry is a kernel argument and is addressed by compile-time index only (a run-time index
+// would move it to scratch).  Held there whole, three terms need about 160 SGPRs of the 102 a wave
+// has (VecEntry alone sits at 96), and the unrolled evaluation spilled 64 of them; so the terms are
+// staged once per workgroup through LDS (stage(), which cross_cov_kernel calls before its barrier)
+// and value() walks them with a wave-uniform run-time loop over the LDS copies: one term's
+// parameters live at a time, one copy of the evaluation's code.
+template <class Term>
+struct SumEntry {
+  static_assert(GP2D_SUM_MAX_TERMS == 3, "stage() names every term");
+  static constexpr int ROWS = Term::ROWS, COLS = Term::COLS;
+  using Keep = typename Term::Keep;
+  struct Staged { Term term; double w; };
+  Term term[GP2D_SUM_MAX_TERMS];
+  double w[GP2D_SUM_MAX_TERMS];
+  int nterms;
+  int add_diag;      // a symmetric mode: a valid diagonal pair gets diag_add
+  double diag_add;
+  __device__ __forceinline__ static Staged* staged() {
+    __shared__ Staged s[GP2D_SUM_MAX_TERMS];
+    return s;
+  }
+  __device__ __forceinline__ void stage() const {
+    if (threadIdx.x == 0) {
+      staged()[0] = {term[0], w[0]};
+      staged()[1] = {term[1], w[1]};
+      staged()[2] = {term[2], w[2]};
+    }
+  }
+  __device__ __forceinline__ decltype(auto) layout() const { return term[0].layout(); }
+  __device__ __forceinline__ bool skip(int64_t i, int64_t jt, int64_t na_pad) const { return term[0].skip(i, jt, na_pad); }
+  __device__ __forceinline__ Keep keep(int64_t i, int64_t j) const { return term[0].keep(i, j); }
+  __device__ __forceinline__ int64_t col(int64_t j, int c, int64_t nb_pad) const { return term[0].col(j, c, nb_pad); }
+  __device__ __forceinline__ void value(const Point3& a, const Point3& b, bool diag, double (&v)[ROWS][COLS]) const {
+#pragma unroll 1
+    for (int t = 0; t < nterms; ++t) {   // wave-uniform trip count, nterms ≥ 1
+      const Staged st = staged()[t];
+      double tv[ROWS][COLS];
+      st.term.value(a, b, diag, tv);
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int c = 0; c < COLS; ++c) v[r][c] = t ? v[r][c] + st.w * tv[r][c] : st.w * tv[r][c];
+    }
+    if (add_diag && diag) {
+#pragma unroll
+      for (int r = 0; r < (ROWS < COLS ? ROWS : COLS); ++r) v[r][r] += diag_add;
+    }
+  }
+  __device__ __forceinline__ void padded(bool diag, double (&v)[ROWS][COLS]) const { term[0].padded(diag, v); }
+};
+
+// The sum of 2×2 blocks: VecEntry's modes (symmetric, lower triangle, col_comp) per term, the terms'
+// own diag_add 0.  Unused term slots repeat term 0 (never evaluated).
+inline SumEntry<VecEntry> make_sum_vec_entry(const gp2d_kernel_t* k, double diag_add, int symmetric, int col_comp) {
+  SumEntry<VecEntry> e;
+  e.nterms = k->nterms;
+  e.add_diag = symmetric != 0;
+  e.diag_add = diag_add;
+  for (int t = 0; t < GP2D_SUM_MAX_TERMS; ++t) {
+    const int s = t < k->nterms ? t : 0;
+    e.term[t] = VecEntry{make_vec_params(sum_term(k, s)), 0.0, symmetric, col_comp};
+    e.w[t] = sum_weight(k, s);
+  }
+  return e;
+}
 
 // One value per pair: sklearn's sum of ARD RBF terms.
 struct ArdEntry : StoresAll {

@@ -62,4 +62,25 @@ inline FieldEntry make_field_entry(const gp2d_kernel_t* k, int field) {
   return p;
 }
 
+// true where the field vanishes by the kernel's kind (δ of DIVFREE, ζ of CURLFREE)
+inline bool field_vanishes(const gp2d_kernel_t* k, int field) {
+  return field_weight(k, field) == 0.0 && k->kind != GP2D_KIND_MIXED;
+}
+
+// A sum's field cross-covariance: Σ_t w_t·(term t's).  A term in which the field vanishes by kind
+// contributes exact zeros whatever its unused length scale holds.
+inline SumEntry<FieldEntry> make_sum_field_entry(const gp2d_kernel_t* k, int field) {
+  SumEntry<FieldEntry> e;
+  e.nterms = k->nterms;
+  e.add_diag = 0;
+  e.diag_add = 0.0;
+  for (int t = 0; t < GP2D_SUM_MAX_TERMS; ++t) {
+    const int s = t < k->nterms ? t : 0;
+    e.term[t] = make_field_entry(sum_term(k, s), field);
+    if (field_vanishes(sum_term(k, s), field)) e.term[t].il2 = e.term[t].w4 = 0.0;
+    e.w[t] = sum_weight(k, s);
+  }
+  return e;
+}
+
 }  // namespace gp2d

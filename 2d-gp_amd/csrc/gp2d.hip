@@ -94,11 +94,42 @@ struct TimedLaunch {
 
 // coordinates per point: (x1, x2), (t, x1, x2), or the ARD dimension
 static int point_dim(const gp2d_kernel_t* k) {
+  if (is_sum_family(k)) k = sum_term(k, 0);   // every term shares the family
   return k->family == GP2D_FAMILY_VECTOR2D ? 2 : (k->family == GP2D_FAMILY_VECTOR_ST ? 3 : k->dim);
+}
+
+static int validate_kernel(const gp2d_kernel_t* k);
+
+// A sum's descriptor array (include/gp2d.h): the header, then every term.
+static int validate_sum(const gp2d_kernel_t* k) {
+  GP2D_REQUIRE(k->nterms >= 1 && k->nterms <= GP2D_SUM_MAX_TERMS, "sum: nterms must be 1..3");
+  for (int t = 0; t < k->nterms; ++t) {
+    const gp2d_kernel_t* kt = sum_term(k, t);
+    GP2D_REQUIRE(!is_sum_family(kt), "sum: a term must not be a sum itself");
+    GP2D_REQUIRE(kt->family != GP2D_FAMILY_ARD_RBF, "sum: ARD terms are not supported (vector families only)");
+    GP2D_REQUIRE(kt->family == sum_term(k, 0)->family,
+                 "sum: the terms must be all VECTOR2D or all VECTOR_ST, not mixed");
+    GP2D_REQUIRE(sum_weight(k, t) > 0.0, "sum: every weight must be > 0");
+    if (validate_kernel(kt) != 0) {
+      set_error("sum: term " + std::to_string(t) + " is invalid: " + g_err);
+      return -2;
+    }
+  }
+  return 0;
+}
+
+// Entries without a sum instantiation refuse one on the host, before any launch.
+static int refuse_sum(const gp2d_kernel_t* k, const char* entry) {
+  if (k != nullptr && is_sum_family(k)) {
+    set_error(std::string(entry) + ": a kernel sum (GP2D_FAMILY_VECTOR_SUM) is not supported by this entry");
+    return -2;
+  }
+  return 0;
 }
 
 static int validate_kernel(const gp2d_kernel_t* k) {
   GP2D_REQUIRE(k != nullptr, "kernel descriptor is NULL");
+  if (is_sum_family(k)) return validate_sum(k);
   if (is_vector_family(k)) {
     GP2D_REQUIRE(k->kind >= 0 && k->kind <= 3, "vector2d kind must be 0..3");
     GP2D_REQUIRE(k->l_df > 0.0, "l_df must be > 0");
@@ -122,6 +153,7 @@ static int validate_kernel(const gp2d_kernel_t* k) {
 // the two parts; kss > 0).  GP_laser's free `rate` outside that range is still accepted by the
 // FP64 engine; the Ozaki entry points reject it.
 static int validate_ozaki_kernel(const gp2d_kernel_t* k) {
+  GP2D_CHECK(refuse_sum(k, "ozaki"));   // no K* instantiation, scale bound or error model for sums
   GP2D_CHECK(validate_kernel(k));
   GP2D_REQUIRE(is_vector_family(k), "ozaki: vector families only");
   if (k->kind == GP2D_KIND_MIXED)
@@ -147,11 +179,14 @@ static int assemble_impl(const double* xa, int64_t na, int64_t na_pad, const dou
   GP2D_REQUIRE(na_pad % PT_TILE == 0 && nb_pad % PT_TILE == 0, "padded point counts must be multiples of 64");
   GP2D_REQUIRE(na <= na_pad && nb <= nb_pad && na >= 0 && nb >= 0, "point counts exceed padded counts");
   if (na_pad == 0 || nb_pad == 0) return 0;
-  const int bd = is_vector_family(k) ? 2 : 1;
+  const int bd = gp2d_block_dim(k);
   GP2D_REQUIRE(ld >= bd * nb_pad, "assemble: ld must be >= block_dim × nb_pad");
   GP2D_REQUIRE(symmetric >= 0 && symmetric <= ASM_LOWER, "symmetric must be 0, 1 or 2");
   GP2D_REQUIRE(symmetric != ASM_LOWER || (bd == 2 && xa == xb && na == nb && na_pad == nb_pad),
                "symmetric = 2 (lower block triangle) needs a vector kernel and xa == xb");
+  if (is_sum_family(k))   // its own instantiation: the one-term path stays VecEntry's
+    return launch_cross_cov(make_sum_vec_entry(k, diag_add, symmetric, -1), xa, na, na_pad, xb, nb, nb_pad, out, ld,
+                            0, nb_pad, s);
   if (bd == 2)
     return launch_cross_cov(VecEntry{make_vec_params(k), diag_add, symmetric, -1}, xa, na, na_pad, xb, nb, nb_pad,
                             out, ld, 0, nb_pad, s);
@@ -261,6 +296,16 @@ int gp2d_block_dim(const gp2d_kernel_t* k) { return (k && k->family == GP2D_FAMI
 
 double gp2d_kernel_diag(const gp2d_kernel_t* k) {
   if (!k) return 0.0;
+  if (is_sum_family(k)) {   // Σ w_t·diag_t, the first term without an add (a one-term sum of weight 1: its term's)
+    if (k->nterms < 1 || k->nterms > GP2D_SUM_MAX_TERMS) return 0.0;
+    double s = 0.0;
+    for (int t = 0; t < k->nterms; ++t) {
+      if (is_sum_family(sum_term(k, t))) return 0.0;
+      const double d = sum_weight(k, t) * gp2d_kernel_diag(sum_term(k, t));
+      s = t ? s + d : d;
+    }
+    return s;
+  }
   if (k->family == GP2D_FAMILY_ARD_RBF) {
     double s = 0.0;
     for (int t = 0; t < k->nterms; ++t) s += k->var[t];
@@ -285,7 +330,7 @@ int gp2d_assemble(const double* xa, int64_t na, int64_t na_pad, const double* xb
 int gp2d_assemble_cols(const double* x, int64_t n, int64_t n_pad, const gp2d_kernel_t* k, double diag_add,
                        double* out, int64_t ld, int64_t c0, int64_t ncols, void* stream) {
   GP2D_CHECK(validate_kernel(k));
-  GP2D_REQUIRE(is_vector_family(k), "assemble_cols: vector kernel families only");
+  GP2D_REQUIRE(is_vector_family(k) || is_sum_family(k), "assemble_cols: vector kernel families only");
   GP2D_REQUIRE(n_pad % PT_TILE == 0 && n >= 0 && n <= n_pad, "assemble_cols: bad point counts");
   GP2D_REQUIRE(ld >= 2 * n_pad, "assemble_cols: ld too small");
   GP2D_REQUIRE(c0 >= 0 && ncols >= 0 && c0 % 64 == 0 && ncols % 64 == 0 && c0 + ncols <= 2 * n_pad &&
@@ -293,6 +338,9 @@ int gp2d_assemble_cols(const double* x, int64_t n, int64_t n_pad, const gp2d_ker
                "assemble_cols: the column range must be 64-aligned and inside one component");
   if (ncols == 0 || n_pad == 0) return 0;
   const int comp = (int)(c0 / n_pad);
+  if (is_sum_family(k))
+    return launch_cross_cov(make_sum_vec_entry(k, diag_add, 1, comp), x, n, n_pad, x, n, n_pad, out, ld,
+                            c0 - (int64_t)comp * n_pad, ncols, S(stream));
   return launch_cross_cov(VecEntry{make_vec_params(k), diag_add, 1, comp}, x, n, n_pad, x, n, n_pad, out, ld,
                           c0 - (int64_t)comp * n_pad, ncols, S(stream));
 }
@@ -1153,13 +1201,26 @@ int gp2d_predict(const double* W, int64_t n, int64_t ldw, const double* alpha, c
 
 // ------------------------------------------------------- PREDICT (derived fields)
 static bool field_kernel_ok(const gp2d_kernel_t* k) {
+  if (k != nullptr && is_sum_family(k)) {   // a validated sum: every term non-scalar
+    for (int t = 0; t < k->nterms; ++t)
+      if (sum_term(k, t)->kind == GP2D_KIND_SCALAR) return false;
+    return true;
+  }
   return k != nullptr && is_vector_family(k) && k->kind != GP2D_KIND_SCALAR;
 }
 
 double gp2d_field_prior_var(const gp2d_kernel_t* k, int field) {
-  if (!field_kernel_ok(k) || validate_kernel(k) != 0 ||
+  if (validate_kernel(k) != 0 || !field_kernel_ok(k) ||
       (field != GP2D_FIELD_DIVERGENCE && field != GP2D_FIELD_VORTICITY))
     return std::nan("");
+  if (is_sum_family(k)) {   // Σ w_t·var_t
+    double s = 0.0;
+    for (int t = 0; t < k->nterms; ++t) {
+      const double d = sum_weight(k, t) * gp2d_field_prior_var(sum_term(k, t), field);
+      s = t ? s + d : d;
+    }
+    return s;
+  }
   const double w = field_weight(k, field);
   if (w == 0.0) return 0.0;   // the field vanishes by kind (its length scale may be unset)
   const double l = (field == GP2D_FIELD_VORTICITY) ? k->l_df : k->l_cf;
@@ -1188,7 +1249,12 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
   if (m <= 0) return 0;
   GP2D_REQUIRE(aligned16(W), "predict_field: W must be 16-byte aligned");
   hipStream_t s = S(stream);
-  if (field_weight(k, field) == 0.0 && k->kind != GP2D_KIND_MIXED) {
+  bool vanishes = !is_sum_family(k) && field_vanishes(k, field);
+  if (is_sum_family(k)) {   // only where the field vanishes in every term
+    vanishes = true;
+    for (int t = 0; t < k->nterms; ++t) vanishes = vanishes && field_vanishes(sum_term(k, t), field);
+  }
+  if (vanishes) {
     // div-free flow has no divergence, curl-free flow no vorticity: exact zeros, no GEMM
     if (hipMemsetAsync(mean, 0, sizeof(double) * (size_t)m, s) != hipSuccess ||
         (compute_var && hipMemsetAsync(var, 0, sizeof(double) * (size_t)m, s) != hipSuccess)) {
@@ -1197,15 +1263,22 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
     }
     return 0;
   }
-  const FieldEntry fe = make_field_entry(k, field);
   // one component per target: the prior is the field's prior variance, no noise, no clipping; untimed
   ChunkedPredict v;
   v.bd = 1;
   v.prior = gp2d_field_prior_var(k, field);
-  v.assemble = [=](const double* xc, int64_t cv, int64_t cp, double* Ks) {
-    // cov(observations, field) for the chunk: rows = training components, cols = target points
-    return launch_cross_cov(fe, xtr, ntr, ntr_pad, xc, cv, cp, Ks, cp, 0, cp, s);
-  };
+  // cov(observations, field) for the chunk: rows = training components, cols = target points
+  if (is_sum_family(k)) {
+    const SumEntry<FieldEntry> fe = make_sum_field_entry(k, field);
+    v.assemble = [=](const double* xc, int64_t cv, int64_t cp, double* Ks) {
+      return launch_cross_cov(fe, xtr, ntr, ntr_pad, xc, cv, cp, Ks, cp, 0, cp, s);
+    };
+  } else {
+    const FieldEntry fe = make_field_entry(k, field);
+    v.assemble = [=](const double* xc, int64_t cv, int64_t cp, double* Ks) {
+      return launch_cross_cov(fe, xtr, ntr, ntr_pad, xc, cv, cp, Ks, cp, 0, cp, s);
+    };
+  }
   return predict_chunks(v, W, n, ldw, alpha, ntr, xg, point_dim(k), m, compute_var, mean, var, chunk, work, s);
 }
 
@@ -1216,6 +1289,7 @@ int gp2d_grad_prior_cov(const gp2d_kernel_t* k, double out[16]) {
     return -2;
   }
   for (int i = 0; i < 16; ++i) out[i] = std::nan("");
+  GP2D_CHECK(refuse_sum(k, "grad_prior_cov"));
   GP2D_CHECK(validate_kernel(k));
   GP2D_REQUIRE(field_kernel_ok(k), "grad_prior_cov: div-free, curl-free or mixed vector kernels only");
   grad_prior_cov(k, out);
@@ -1227,6 +1301,7 @@ size_t gp2d_predict_grad_workspace(int64_t n, int64_t chunk) { return PredictGra
 int gp2d_predict_grad(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
                       int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, int compute_cov,
                       double* mean, double* cov, int64_t chunk, void* work, size_t work_bytes, void* stream) {
+  GP2D_CHECK(refuse_sum(k, "predict_grad"));
   GP2D_CHECK(validate_kernel(k));
   GP2D_REQUIRE(field_kernel_ok(k), "predict_grad: div-free, curl-free or mixed vector kernels only");
   GP2D_REQUIRE(n == 2 * ntr_pad, "predict_grad: n must equal 2 × ntr_pad");
@@ -1259,6 +1334,7 @@ size_t gp2d_predict_cov_workspace(int64_t n, int64_t m) { return PredictCovWork(
 int gp2d_predict_cov(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
                      int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, double diag_add,
                      double* mean, double* cov, int64_t ldc, void* work, size_t work_bytes, void* stream) {
+  GP2D_CHECK(refuse_sum(k, "predict_cov"));
   GP2D_CHECK(validate_kernel(k));
   GP2D_REQUIRE(field_kernel_ok(k), "predict_cov: div-free, curl-free or mixed vector kernels only");
   GP2D_REQUIRE(n == 2 * ntr_pad, "predict_cov: n must equal 2 × ntr_pad");
@@ -1812,6 +1888,8 @@ int gp2d_lml(const double* W, int64_t n, int64_t ldw, const double* alpha, const
 
 int gp2d_lml_grad_count(const gp2d_kernel_t* k) {
   if (validate_kernel(k) != 0) return -2;
+  if (is_sum_family(k))   // per term its weight and its own entries without noise, then noise
+    return k->nterms * (sum_term(k, 0)->family == GP2D_FAMILY_VECTOR_ST ? 6 : 4) + 1;
   if (k->family == GP2D_FAMILY_VECTOR2D) return 4;
   if (k->family == GP2D_FAMILY_VECTOR_ST) return 6;
   return k->nterms * (1 + k->dim) + 1;
@@ -1843,6 +1921,16 @@ SlotMap grad_slots(const gp2d_kernel_t* k, bool with_noise) {
   return m;
 }
 
+// One term of a sum: its weight, then the term's own entries in its family's order; the noise
+// (the last term's launch only) after them.
+SlotMap sum_term_slots(const gp2d_kernel_t* kt, bool with_noise) {
+  SlotMap m = grad_slots(kt, with_noise);
+  for (int g = m.ng; g > 0; --g) m.slot[g] = m.slot[g - 1];
+  m.slot[0] = SumVecFamily::WEIGHT;
+  ++m.ng;
+  return m;
+}
+
 // A pair gradient (lml.hpp): weights ⊙ ∂K/∂θ summed over the pairs of the na row points xa and the
 // nb column points xb (ncols_pad: nb padded to whole tiles) into `partial`, then out[g] = scale ·
 // the blocks' sum of output g's slot.
@@ -1851,6 +1939,21 @@ int launch_pair_grad(const gp2d_kernel_t* k, const double* xa, int64_t na, const
                      int64_t ncols_pad, const Weights& weights, double* partial, double scale, bool with_noise,
                      double* out, hipStream_t s) {
   const dim3 grid((unsigned)(ncols_pad / PT_TILE), (unsigned)((na + LML_ROWS - 1) / LML_ROWS));
+  if (is_sum_family(k)) {
+    // one launch per term into the same partials (stream order keeps them apart), each term's
+    // outputs at its offset; the noise slot, equal in every launch, is taken from the last one
+    for (int t = 0; t < k->nterms; ++t) {
+      const gp2d_kernel_t* kt = sum_term(k, t);
+      const SumVecFamily fam{{make_vec_params(kt), kt->l_df, kt->l_cf, kt->ls[0][0]}, sum_weight(k, t)};
+      pair_grad_kernel<<<grid, 256, 0, s>>>(xa, na, xb, nb, fam, weights, partial);
+      GP2D_CHECK(check_launch("pair_grad_kernel"));
+      const SlotMap sm = sum_term_slots(kt, with_noise && t == k->nterms - 1);
+      grad_sum_kernel<<<sm.ng, 256, 0, s>>>(partial, grad_blocks(ncols_pad, na), sm, scale, out);
+      GP2D_CHECK(check_launch("grad_sum_kernel"));
+      out += sm.ng;
+    }
+    return 0;
+  }
   if (is_vector_family(k)) {
     const VecFamily fam{{make_vec_params(k), k->l_df, k->l_cf, k->ls[0][0]}};
     pair_grad_kernel<<<grid, 256, 0, s>>>(xa, na, xb, nb, fam, weights, partial);

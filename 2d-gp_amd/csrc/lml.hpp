@@ -20,7 +20,8 @@
 // the weights.  Both run on one kernel, pair_grad_kernel<Family, Weights>, which owns the thread
 // mapping, the bounds tests, the accumulators, the block reduction and the partial's address; its
 // two axes are policy structs passed by value:
-//   Family   VecFamily (6 slots, three weights per pair) or ArdFamily (9 slots, one weight);
+//   Family   VecFamily (6 slots, three weights per pair), SumVecFamily (one term of a sum: 7 slots)
+//            or ArdFamily (9 slots, one weight);
 //   Weights  TraceWeights (the stored triangle above; the diagonal also feeds the noise slot) or
 //            DenseWeights (dL/dK).
 // Per-block partial sums are reduced in a fixed order (grad_sum_kernel), so the result is
@@ -162,7 +163,7 @@ __device__ __forceinline__ void block_reduce_vec(const double* v, double (*red)[
 
 // Gradient accumulators live in fixed slots so that every index is a compile-time constant
 // (no scratch): vector families 0 = l_df, 1 = l_cf, 2 = ratio, 3 = noise, 4 = var_t, 5 = l_t
-// (spatio-temporal product); ARD t·4 = var_t, t·4+1+d = ls_td, 8 = noise.  SlotMap lists the
+// (spatio-temporal product), 6 = weight (a sum's term); ARD t·4 = var_t, t·4+1+d = ls_td, 8 = noise.  SlotMap lists the
 // slots in the output order.
 struct SlotMap {
   int ng;
@@ -230,6 +231,23 @@ struct VecFamily {
   }
 };
 
+// One term of a sum of vector kernels (GP2D_FAMILY_VECTOR_SUM), a launch per term: K = w_t·K_t, so
+// VecFamily's accumulation with the pair's weights scaled by w_t, and slot 6 = ∂/∂w_t = Σ weights ⊙ K_t.
+struct SumVecFamily {
+  static constexpr int NSLOT = 7, NOISE = 3, WEIGHT = 6;
+  using Weight = VecWeight;
+  VecGradParams gp;
+  double wt;
+  __device__ __forceinline__ const VecParams& layout() const { return gp.p; }
+  __device__ __forceinline__ void accum(const Point3& a, const Point3& b, const Weight& w, double* acc) const {
+    const double dt = a.c[0] - b.c[0], d1 = a.c[1] - b.c[1], d2 = a.c[2] - b.c[2];
+    double k11, k12, k22;
+    vec_block_st(gp.p, dt, d1, d2, k11, k12, k22);
+    acc[WEIGHT] += w.w11 * k11 + w.w12 * k12 + w.w22 * k22;
+    vec_grad_accum(gp, dt, d1, d2, wt * w.w11, wt * w.w12, wt * w.w22, acc);
+  }
+};
+
 // ARD family: slots t·4 + {0: var, 1+d: ls_d} and 8, one weight per pair.
 struct ArdFamily {
   static constexpr int NSLOT = LML_MAXG, NOISE = 8;
@@ -254,10 +272,18 @@ struct TraceWeights {
   int64_t np;
   struct VecCol { double u, v; };
   __device__ __forceinline__ VecCol column(const VecFamily&, int64_t q) const { return {alpha[q], alpha[np + q]}; }
+  __device__ __forceinline__ VecCol column(const SumVecFamily&, int64_t q) const { return {alpha[q], alpha[np + q]}; }
   __device__ __forceinline__ double column(const ArdFamily&, int64_t q) const { return alpha[q]; }
-  // vu entry (np+p, q): always in the stored triangle (uv is its transpose); uu, vv: p ≥ q
   __device__ __forceinline__ bool pair(const VecFamily&, int64_t p, int64_t q, const VecCol& aq, VecWeight& w,
                                        double* acc) const {
+    return vec_pair(p, q, aq, w, acc);
+  }
+  __device__ __forceinline__ bool pair(const SumVecFamily&, int64_t p, int64_t q, const VecCol& aq, VecWeight& w,
+                                       double* acc) const {
+    return vec_pair(p, q, aq, w, acc);
+  }
+  // vu entry (np+p, q): always in the stored triangle (uv is its transpose); uu, vv: p ≥ q
+  __device__ __forceinline__ bool vec_pair(int64_t p, int64_t q, const VecCol& aq, VecWeight& w, double* acc) const {
     const double apu = alpha[p], apv = alpha[np + p];
     const double* cu = C + p * n;          // row p (u)
     const double* cv = C + (np + p) * n;   // row np+p (v)
@@ -289,6 +315,10 @@ struct DenseWeights {
   struct NoCol {};
   template <class Family>
   __device__ __forceinline__ NoCol column(const Family&, int64_t) const { return {}; }
+  __device__ __forceinline__ bool pair(const SumVecFamily&, int64_t p, int64_t q, NoCol c, VecWeight& w,
+                                       double* acc) const {
+    return pair(VecFamily{}, p, q, c, w, acc);
+  }
   __device__ __forceinline__ bool pair(const VecFamily&, int64_t p, int64_t q, NoCol, VecWeight& w, double*) const {
     const double* g0 = G + p * ld;
     const double* g1 = G + (na + p) * ld;

@@ -14,7 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GP2D_LIB", os.path.join(_HERE, "libgp2d.so"))
 ABI_VERSION = 11         # GP2D_ABI_VERSION in include/gp2d.h
 
-FAMILY_VECTOR2D, FAMILY_ARD_RBF, FAMILY_VECTOR_ST = 0, 1, 2
+FAMILY_VECTOR2D, FAMILY_ARD_RBF, FAMILY_VECTOR_ST, FAMILY_VECTOR_SUM = 0, 1, 2, 3
+SUM_MAX_TERMS = 3        # GP2D_SUM_MAX_TERMS
 KIND_SCALAR, KIND_DIVFREE, KIND_CURLFREE, KIND_MIXED = 0, 1, 2, 3
 VAR_LATENT, VAR_NOISY, VAR_CLIPPED = 0, 1, 2
 FIELD_DIVERGENCE, FIELD_VORTICITY = 1, 2
@@ -82,7 +83,14 @@ _I64 = ctypes.c_int64
 _D = ctypes.c_double
 _I = ctypes.c_int
 _SZ = ctypes.c_size_t
-_KP = ctypes.POINTER(KernelDesc)
+
+
+
+class _KP(ctypes.c_void_p):
+    """const gp2d_kernel_t*: ctypes.byref of one KernelDesc, or of a sum's (KernelDesc * (1 + T))
+    array (vector_sum_kernel_desc), which a POINTER(KernelDesc) argument would refuse."""
+
+
 
 _SIGS = {
     "gp2d_abi_version": (_I, []),
@@ -260,3 +268,22 @@ def ard_kernel_desc(variances, lengthscales) -> KernelDesc:
         for d in range(dim):
             k.ls[t][d] = float(ls[d])
     return k
+
+
+def vector_sum_kernel_desc(terms, weights):
+    """A sum of vector kernels Σ_t w_t·K(term t) (GP2D_FAMILY_VECTOR_SUM): the (KernelDesc * (1 + T))
+    array the library reads — the header (nterms = T, ls[0][t] = w_t), then copies of the T term
+    descriptors (all vector2d or all vector_st).  Pass it with ctypes.byref like a single descriptor."""
+    terms = list(terms)
+    weights = [float(w) for w in weights]
+    if not 1 <= len(terms) <= SUM_MAX_TERMS:
+        raise ValueError(f"a kernel sum has 1..{SUM_MAX_TERMS} terms")
+    if len(weights) != len(terms):
+        raise ValueError("a kernel sum needs one weight per term")
+    arr = (KernelDesc * (1 + len(terms)))()
+    arr[0].family = FAMILY_VECTOR_SUM
+    arr[0].nterms = len(terms)
+    for t, (k, w) in enumerate(zip(terms, weights)):
+        arr[0].ls[0][t] = w
+        ctypes.memmove(ctypes.byref(arr[1 + t]), ctypes.byref(k), ctypes.sizeof(KernelDesc))
+    return arr

@@ -134,6 +134,10 @@ class KernelSpec:
         Kt(var_t, l_t) × (the vector2d kernel of `kind`) on (T, Y, X) points — GPy
         `Kt(...) * nonDivK(2, [1, 2], ℓ)` (scratch.py:506-508; Kt myKernel.py:337-363),
         standing in for the reference's missing myKernel2 (krig.py:397-404)
+    family 'vector_sum': Σ_t weights[t]·terms[t], 1-3 terms that are all 'vector2d' or all
+        'vector_st' (kinds may differ) — the reference's k = k2 + k2 + … (krig.py:405-407), one term
+        per flow scale.  FP64 engine only.  term(t) is the one-term sum (w_t, term t): as a
+        predict's kernel on the sum's fit it gives the posterior of term t's contribution alone.
     """
     family: str = "vector2d"
     kind: str = "df"
@@ -144,11 +148,40 @@ class KernelSpec:
     lengthscales: tuple = ()
     var_t: float = 1.0
     l_t: float = 1.0
+    terms: tuple = ()
+    weights: tuple = ()
 
     _KINDS = {"scalar": N.KIND_SCALAR, "df": N.KIND_DIVFREE, "cf": N.KIND_CURLFREE, "mixed": N.KIND_MIXED,
               0: N.KIND_SCALAR, 1: N.KIND_DIVFREE, 2: N.KIND_CURLFREE, 3: N.KIND_MIXED}
 
-    def desc(self) -> N.KernelDesc:
+    @property
+    def is_sum(self) -> bool:
+        return self.family == "vector_sum"
+
+    def _sum_terms(self) -> tuple:
+        """The terms of a sum, checked: 1..3, one vector family, one weight each."""
+        terms, weights = tuple(self.terms), tuple(self.weights)
+        if not 1 <= len(terms) <= N.SUM_MAX_TERMS:
+            raise ValueError(f"a kernel sum has 1..{N.SUM_MAX_TERMS} terms")
+        if len(weights) != len(terms):
+            raise ValueError("a kernel sum needs one weight per term")
+        fams = {t.family for t in terms}
+        if len(fams) != 1 or not fams <= {"vector2d", "vector_st"}:
+            raise ValueError("the terms of a kernel sum must be all 'vector2d' or all 'vector_st'")
+        return terms
+
+    def term(self, t: int) -> "KernelSpec":
+        """The one-term sum (w_t, term t) of a sum: the kernel of term t's posterior (predict(term=t))."""
+        terms = self._sum_terms()
+        if not 0 <= int(t) < len(terms):
+            raise ValueError(f"term must be in 0..{len(terms) - 1}")
+        return KernelSpec(family="vector_sum", terms=(terms[int(t)],), weights=(float(self.weights[int(t)]),))
+
+    def desc(self):
+        """The library's descriptor: one KernelDesc, or a sum's (KernelDesc * (1 + T)) array; both
+        pass by ctypes.byref."""
+        if self.family == "vector_sum":
+            return N.vector_sum_kernel_desc([t.desc() for t in self._sum_terms()], self.weights)
         if self.family == "vector2d":
             return N.vector_kernel_desc(self._KINDS[self.kind], self.l_df, self.l_cf, self.ratio)
         if self.family == "ard":
@@ -160,7 +193,7 @@ class KernelSpec:
 
     @property
     def is_vector(self) -> bool:
-        return self.family in ("vector2d", "vector_st")
+        return self.family in ("vector2d", "vector_st", "vector_sum")
 
     @property
     def block_dim(self) -> int:
@@ -168,6 +201,8 @@ class KernelSpec:
 
     @property
     def input_dim(self) -> int:
+        if self.family == "vector_sum":
+            return self._sum_terms()[0].input_dim
         if self.family == "vector2d":
             return 2
         return 3 if self.family == "vector_st" else len(self.lengthscales[0])
@@ -185,6 +220,7 @@ class KernelSpec:
         """(4, 4) prior covariance of the velocity gradient tensor at one point, components
         GRADIENT_COMPONENTS (gp2d_grad_prior_cov): singular along the divergence for 'df' and along
         the vorticity for 'cf'.  ValueError for the scalar kind and the ARD family."""
+        _refuse_sum(self, "grad_prior_cov")
         _require_velocity(self, "the velocity gradient needs a div-free, curl-free or mixed vector kernel "
                                 "(the scalar kind and the ARD family have none)")
         out = (ctypes.c_double * 16)()
@@ -454,7 +490,17 @@ class _Staged:
     perm: torch.Tensor | None
 
 
+def _refuse_sum(kernel: KernelSpec, entry: str):
+    """ValueError for an entry that has no kernel-sum form (the gradient tensor, the joint
+    covariance, the int8 engine)."""
+    if kernel.is_sum:
+        raise ValueError(f"{entry} does not support a kernel sum (family 'vector_sum')")
+
+
 def _check_family(kernel: KernelSpec, variance: str):
+    if variance == "ozaki" and kernel.is_sum:
+        raise ValueError("the ozaki variance engine does not support a kernel sum (family 'vector_sum'): "
+                         "use variance='f64'")
     if variance == "ozaki" and not kernel.is_vector:
         raise ValueError("the ozaki variance engine supports the vector families only")
 
@@ -894,10 +940,11 @@ class Predictor:
                 and self.gp.kernel.block_dim == gp.kernel.block_dim)
 
     def __call__(self, xg, var_mode: str = "latent", compute_var: bool = True, out=None,
-                 planes: KstarPlanes | None = None, reuse_grid: bool = False):
+                 planes: KstarPlanes | None = None, reuse_grid: bool = False, term: int | None = None):
         """planes: K* residue planes of this same grid from kstar_planes() (ozaki engine):
         the variance GEMMs read them and the K* kernel runs mean-only (same results as without).
-        reuse_grid: the grid is the one of the previous call, unmodified (_grid_order)."""
+        reuse_grid: the grid is the one of the previous call, unmodified (_grid_order).
+        term: the posterior of term t's contribution alone, from a kernel sum's fit (predict)."""
         gp = self.gp
         L = N.lib()
         d, bd = gp.kernel.input_dim, gp.kernel.block_dim
@@ -908,7 +955,7 @@ class Predictor:
             var = torch.empty(bd * m, dtype=torch.float64, device=gp.device)
         else:
             mean, var = out
-        desc = gp.kernel.desc()
+        desc = _term_kernel(gp, term, var_mode).desc()
         if self.ozaki and "ozaki" in gp.extra:
             wres, rowscale, nmod, kbits = gp.extra["ozaki"]
             self._ozaki_workspace(nmod)
@@ -947,8 +994,25 @@ class Predictor:
         return mean, (var if compute_var else None)
 
 
-def predict(gp: GPFit, xg, var_mode: str = "latent", compute_var: bool = True, chunk: int = 8192):
-    return _predictor_for(None, gp, chunk)(xg, var_mode=var_mode, compute_var=compute_var)
+def _term_kernel(gp: GPFit, term: int | None, var_mode: str = "latent") -> KernelSpec:
+    """The kernel a predict passes to the library: the fit's, or for term=t of a kernel sum's fit
+    the one-term sum (w_t, term t).  With y = Σ_t f_t + ε, cov(f_t(g), y) = w_t·K_t(g, X), so the
+    fit's W and α with that kernel give term t's posterior mean w_t·K_t*·α and latent variance
+    w_t·diag_t − ‖W·w_t·K_t*ᵀ‖²; a term is never observed, so there is no noisy variance."""
+    if term is None:
+        return gp.kernel
+    if not gp.kernel.is_sum:
+        raise ValueError("term= needs a fit of a kernel sum (family 'vector_sum')")
+    if var_mode != "latent":
+        raise ValueError("term= gives the latent variance only (var_mode='latent'): a term is never observed")
+    return gp.kernel.term(term)
+
+
+def predict(gp: GPFit, xg, var_mode: str = "latent", compute_var: bool = True, chunk: int = 8192,
+            term: int | None = None):
+    """Posterior mean and variance at xg ([u…, v…]).  term=t (a kernel sum's fit): the posterior of
+    term t's contribution alone (_term_kernel); the term means add up to the full mean."""
+    return _predictor_for(None, gp, chunk)(xg, var_mode=var_mode, compute_var=compute_var, term=term)
 
 
 FIELDS = ("divergence", "vorticity")
@@ -958,7 +1022,8 @@ _FIELD_CODES = {"divergence": N.FIELD_DIVERGENCE, "vorticity": N.FIELD_VORTICITY
 def _require_velocity(kernel: KernelSpec, needs: str, gp: GPFit | None = None, entry: str = ""):
     """ValueError(needs) unless the kernel is a div-free, curl-free or mixed vector kernel; for a
     fit, also unless it still has the factor W that `entry` contracts with."""
-    if not kernel.is_vector or kernel._KINDS[kernel.kind] == N.KIND_SCALAR:
+    kinds = [t.kind for t in kernel._sum_terms()] if kernel.is_sum else [kernel.kind]
+    if not kernel.is_vector or any(kernel._KINDS[k] == N.KIND_SCALAR for k in kinds):
         raise ValueError(needs)
     if gp is not None and gp.W is None:
         raise ValueError(f"{entry} needs the fit's factor W = L⁻¹ (this fit keeps only its int8 planes)")
@@ -974,7 +1039,8 @@ def _field_code(kernel: KernelSpec, field: str, gp: GPFit | None = None) -> int:
     return _FIELD_CODES[field]
 
 
-def predict_field(gp: GPFit, xg, field: str, compute_var: bool = True, chunk: int = 8192):
+def predict_field(gp: GPFit, xg, field: str, compute_var: bool = True, chunk: int = 8192,
+                  term: int | None = None):
     """Posterior mean and latent variance of a derived scalar field of the fitted velocity, at the
     points xg: (mean, var) device tensors of shape (m,), var None if not asked.
 
@@ -989,7 +1055,8 @@ def predict_field(gp: GPFit, xg, field: str, compute_var: bool = True, chunk: in
 
     Works for fits of either variance engine — the contraction runs on the FP64 engine from the
     fit's W; gp.x, gp.alpha and gp.W share one point order.  ValueError for the scalar kind, the
-    ARD family, and a fit without W (a job stream's receiving rank keeps only the int8 planes)."""
+    ARD family, and a fit without W (a job stream's receiving rank keeps only the int8 planes).
+    term=t (a kernel sum's fit): the field of term t's contribution alone (_term_kernel)."""
     code = _field_code(gp.kernel, field, gp)
     L = N.lib()
     G = _as_points(xg, gp.kernel.input_dim, gp.device)
@@ -1000,7 +1067,7 @@ def predict_field(gp: GPFit, xg, field: str, compute_var: bool = True, chunk: in
     work = _workspace(wbytes, gp.device)
     mean = torch.empty(m, dtype=torch.float64, device=gp.device)
     var = torch.empty(m, dtype=torch.float64, device=gp.device) if compute_var else None
-    desc = gp.kernel.desc()
+    desc = _term_kernel(gp, term).desc()
     N.check(L.gp2d_predict_field(*_f64_fit_args(gp, G, desc), code, int(bool(compute_var)), _ptr(mean),
                                  None if var is None else _ptr(var), chunk, _ptr(work), wbytes,
                                  _stream_handle(gp.device)), "gp2d_predict_field")
@@ -1030,7 +1097,8 @@ def predict_gradient(gp: GPFit, xg, compute_cov: bool = True, chunk: int = 8192)
     No noise or clipping mode: a gradient is never observed.
 
     Works for fits of either variance engine, like predict_field.  ValueError for the scalar kind,
-    the ARD family, and a fit without W."""
+    the ARD family, a kernel sum, and a fit without W."""
+    _refuse_sum(gp.kernel, "predict_gradient")
     _require_velocity(gp.kernel, "the velocity gradient needs a div-free, curl-free or mixed vector kernel "
                                  "(the scalar kind and the ARD family have none)", gp, "predict_gradient")
     L = N.lib()
@@ -1088,6 +1156,7 @@ def flow_diagnostics(mean, cov=None, names=DIAGNOSTICS) -> dict:
 
 def _predict_cov_padded(gp: GPFit, xg, diag_add: float):
     """gp2d_predict_cov: (mean (2m,), the padded q × q covariance, m, mp) on the device."""
+    _refuse_sum(gp.kernel, "predict_cov")
     _require_velocity(gp.kernel, "the joint covariance needs a div-free, curl-free or mixed vector kernel "
                                  "(the scalar kind and the ARD family are not supported)", gp, "predict_cov")
     L = N.lib()
@@ -1275,6 +1344,7 @@ def krige_jobs(jobs, variance: str = "ozaki", chunk: int = 8192, var_mode: str =
     first, it = _peek(iter(jobs))
     if first is None:
         return
+    _check_family(first[0], variance)   # a kernel sum on the int8 engine: refused before anything is issued
     n_sides, b, targets = _job_schedule(*_job_mode(first, variance, compute_var, fits_ahead, batch_fits, batch_ahead))
     sides = [side_stream(dev) for _ in range(n_sides)]
     prev_sets = N.lib().gp2d_factor_sets(n_sides) if n_sides > 1 else None   # one internal factor set per side stream
@@ -1543,7 +1613,13 @@ def hand_over(gp: GPFit, stats: dict | None, main=None):
 def param_names(kernel: KernelSpec) -> tuple:
     """Gradient / parameter order of log_marginal_likelihood: vector2d (l_df, l_cf, ratio, noise);
     vector_st (l_df, l_cf, ratio, var_t, l_t, noise); ARD per term (variance, lengthscale_0..D−1),
-    then noise (GPy param_array order, krig.py:459-466)."""
+    then noise (GPy param_array order, krig.py:459-466); a kernel sum per term t (weight_t, l_df_t,
+    l_cf_t, ratio_t[, var_t_t, l_t_t]), then noise."""
+    if kernel.family == "vector_sum":
+        names = []
+        for t, k in enumerate(kernel._sum_terms()):
+            names += [f"weight_{t}"] + [f"{n}_{t}" for n in param_names(k)[:-1]]
+        return tuple(names + ["noise"])
     if kernel.family == "vector2d":
         return ("l_df", "l_cf", "ratio", "noise")
     if kernel.family == "vector_st":

@@ -38,8 +38,18 @@ _BAD = 1e25  # objective for a non-positive-definite K_y (rejected by the line s
 
 
 def free_names(kernel: E.KernelSpec, fix=()) -> tuple:
-    """Names (engine.param_names order) of the parameters the optimiser moves."""
-    if kernel.is_vector:
+    """Names (engine.param_names order) of the parameters the optimiser moves.  A kernel sum: per
+    term what its kind uses (suffix _t), and for 'vector2d' terms the weight — a 'vector_st' term's
+    amplitude is its var_t, so its weight stays at its value (1 by convention)."""
+    if kernel.is_sum:
+        names = ()
+        for t, k in enumerate(kernel.terms):
+            used = free_names(k)[:-1]
+            if k.family == "vector2d":
+                used = ("weight",) + used
+            names += tuple(f"{n}_{t}" for n in used)
+        names += ("noise",)
+    elif kernel.is_vector:
         used = {"df": ("l_df",), "scalar": ("l_df",), "cf": ("l_cf",),
                 "mixed": ("l_df", "l_cf", "ratio")}[_kind_name(kernel.kind)]
         if kernel.family == "vector_st":
@@ -56,7 +66,12 @@ def _kind_name(kind):
 
 def get_params(kernel: E.KernelSpec, noise: float) -> dict:
     names = E.param_names(kernel)
-    if kernel.family == "vector2d":
+    if kernel.is_sum:
+        vals = []
+        for k, w in zip(kernel.terms, kernel.weights):
+            vals += [w, *list(get_params(k, 0.0).values())[:-1]]
+        vals.append(noise)
+    elif kernel.family == "vector2d":
         vals = (kernel.l_df, kernel.l_cf, kernel.ratio, noise)
     elif kernel.family == "vector_st":
         vals = (kernel.l_df, kernel.l_cf, kernel.ratio, kernel.var_t, kernel.l_t, noise)
@@ -70,6 +85,13 @@ def get_params(kernel: E.KernelSpec, noise: float) -> dict:
 
 def set_params(kernel: E.KernelSpec, params: dict):
     """(KernelSpec, noise) with `params` (a get_params-style dict) applied."""
+    if kernel.is_sum:
+        terms = []
+        for t, k in enumerate(kernel.terms):
+            own = {n: params[f"{n}_{t}"] for n in E.param_names(k)[:-1]}
+            terms.append(set_params(k, dict(own, noise=0.0))[0])
+        weights = tuple(params[f"weight_{t}"] for t in range(len(terms)))
+        return dataclasses.replace(kernel, terms=tuple(terms), weights=weights), params["noise"]
     if kernel.family == "vector2d":
         k = dataclasses.replace(kernel, l_df=params["l_df"], l_cf=params["l_cf"], ratio=params["ratio"])
         return k, params["noise"]
@@ -84,22 +106,27 @@ def set_params(kernel: E.KernelSpec, params: dict):
     return dataclasses.replace(kernel, variances=tuple(var), lengthscales=tuple(ls)), params["noise"]
 
 
+def _is_ratio(name) -> bool:
+    """ratio, or a sum term's ratio_t: the logistic coordinate; every other parameter is positive."""
+    return name == "ratio" or name.startswith("ratio_")
+
+
 def _to_free(name, v):
-    if name == "ratio":
+    if _is_ratio(name):
         v = min(max(v, 1e-12), 1 - 1e-12)
         return math.log(v / (1 - v))
     return math.log(v)
 
 
 def _from_free(name, z):
-    if name == "ratio":
+    if _is_ratio(name):
         return 1.0 / (1.0 + math.exp(-z))
     return math.exp(z)
 
 
 def _dfree(name, v):
     """d(value)/d(free coordinate)."""
-    return v * (1 - v) if name == "ratio" else v
+    return v * (1 - v) if _is_ratio(name) else v
 
 
 @dataclass

@@ -76,7 +76,9 @@ class Krig:
     kernel: 'df' (divergence-free, GP_scripts divFree=1), 'cf' (curl-free, 2),
     'mixed' (ratio·df + (1−ratio)·cf, GP_laser.py:113), 'scalar' (divFree=0),
     a ``kern.myKernel``/``nonDivK``/``nonRotK`` instance, or an ``engine.KernelSpec``
-    (incl. family='ard' for the sklearn model of krig.scikit_prior).
+    (incl. family='ard' for the sklearn model of krig.scikit_prior, and family='vector_sum', a sum
+    of vector kernels with one term per flow scale: FP64 engine only; predict(term=t) and
+    predict_fields(term=t) give the posterior of term t's contribution alone).
     var_mode: 'latent' (GP_laser.py:128-131), 'gpy' (+noise, GPy model.predict),
     'sklearn' (+noise, clipped at 0, _gpr.py:473-485).
     variance: 'f64' (default) — the FP64-MFMA engine, FP64 arithmetic throughout as in the
@@ -93,6 +95,7 @@ class Krig:
         self.jitchol = int(jitchol)   # GPy jitchol retries on a non-PD K_y (engine.fit)
         if variance == "ozaki" and not self.spec.is_vector:
             raise ValueError("the ozaki variance engine supports the vector kernels only")
+        E._check_family(self.spec, variance)   # a kernel sum: variance="f64" only
         if variance not in E.VARIANCE_ENGINES:
             raise ValueError(f"variance must be one of {E.VARIANCE_ENGINES}")
         self.variance = variance
@@ -137,50 +140,56 @@ class Krig:
             raise RuntimeError("Krig.fit must be called before predict")
 
     # ------------------------------------------------------------------ predict
-    def predict_device(self, Xg, var_mode=None, compute_var=True):
-        """Posterior mean and variance as device tensors ([u..., v...] for vector kernels)."""
+    def predict_device(self, Xg, var_mode=None, compute_var=True, term=None):
+        """Posterior mean and variance as device tensors ([u..., v...] for vector kernels).
+        term=t (a kernel sum): term t's contribution alone, latent variance (a var_mode other than
+        'latent' raises: a term is never observed)."""
         self._check()
-        return self._pred(Xg, var_mode=var_mode or self.var_mode, compute_var=compute_var)
+        if term is not None and var_mode is None:
+            var_mode = "latent"
+        return self._pred(Xg, var_mode=var_mode or self.var_mode, compute_var=compute_var, term=term)
 
-    def predict(self, Xg, var_mode=None, compute_var=True):
+    def predict(self, Xg, var_mode=None, compute_var=True, term=None):
         """(mean, var) numpy arrays of shape (bd·M, 1), as GPy's model.predict returns
-        (krig.py:543-544; f[:M] = u, f[M:] = v, GP_plots.py:768-771)."""
-        mu, var = self.predict_device(Xg, var_mode=var_mode, compute_var=compute_var)
+        (krig.py:543-544; f[:M] = u, f[M:] = v, GP_plots.py:768-771).  term: predict_device's."""
+        mu, var = self.predict_device(Xg, var_mode=var_mode, compute_var=compute_var, term=term)
         mu = _to_numpy(mu)[:, None]
         return mu, (_to_numpy(var)[:, None] if compute_var else None)
 
-    def predict_grid(self, x, y, var_mode=None):
+    def predict_grid(self, x, y, var_mode=None, term=None):
         """GP_laser.py:107-136 on the grid meshgrid(x, y): returns uf, vf, uvar, vvar,
-        each reshaped to [y.size, x.size]."""
+        each reshaped to [y.size, x.size].  term: predict_device's."""
         X, Y = np.meshgrid(x, y)
         pts = np.stack([X.reshape(-1), Y.reshape(-1)], 1)
-        mu, var = self.predict_device(pts, var_mode=var_mode)
+        mu, var = self.predict_device(pts, var_mode=var_mode, term=term)
         mu, var = _to_numpy(mu), _to_numpy(var)
         M = pts.shape[0]
         shp = [np.size(y), -1]
         return (mu[:M].reshape(shp), mu[M:].reshape(shp), var[:M].reshape(shp), var[M:].reshape(shp))
 
-    def predict_fields(self, Xg, fields=E.FIELDS):
+    def predict_fields(self, Xg, fields=E.FIELDS, term=None):
         """Divergence and vorticity of the fitted velocity at the points Xg, with their latent
         variance: {name: (mean, var)} numpy arrays of shape (M,) (engine.predict_field).  For
         points (x1, x2) and observations [f1; f2]: divergence = ∂f1/∂x1 + ∂f2/∂x2, vorticity =
         ∂f2/∂x1 − ∂f1/∂x2 — with points (x, y) and obs [u; v] the usual ∂u/∂x + ∂v/∂y and
         ∂v/∂x − ∂u/∂y; points given as (Y, X) with obs [v; u] give −vorticity.  Replaces the
-        finite differences of a predicted grid: exact, with an error bar, on any set of points."""
+        finite differences of a predicted grid: exact, with an error bar, on any set of points.
+        term=t (a kernel sum): the fields of term t's contribution alone."""
         self._check()
         out = {}
         for name in fields:
-            mu, var = E.predict_field(self.gp, Xg, name, chunk=self.chunk)
+            mu, var = E.predict_field(self.gp, Xg, name, chunk=self.chunk, term=term)
             out[name] = (_to_numpy(mu), _to_numpy(var))
         return out
 
-    def predict_fields_grid(self, x, y):
+    def predict_fields_grid(self, x, y, term=None):
         """predict_fields on the grid meshgrid(x, y) of predict_grid (points (x, y), components
         (u, v)): {name: (mean, var)}, each reshaped to [y.size, x.size]."""
         X, Y = np.meshgrid(x, y)
         pts = np.stack([X.reshape(-1), Y.reshape(-1)], 1)
         shp = [np.size(y), -1]
-        return {name: (mu.reshape(shp), var.reshape(shp)) for name, (mu, var) in self.predict_fields(pts).items()}
+        return {name: (mu.reshape(shp), var.reshape(shp))
+                for name, (mu, var) in self.predict_fields(pts, term=term).items()}
 
     def predict_gradient(self, Xg):
         """The velocity gradient tensor at the points Xg with its joint posterior covariance per
@@ -288,6 +297,8 @@ class Krig:
     @property
     def param_array(self):
         s = self.spec
+        if s.is_sum:   # engine.param_names order: per term its weight and its own entries, then noise
+            return np.array(list(H.get_params(s, self.noise).values()))
         if s.family == "ard":
             hp = []
             for v, ls in zip(s.variances, s.lengthscales):
@@ -308,6 +319,11 @@ class Krig:
                  noise=self.noise, jitter=self.jitter, jitchol=self.jitchol,
                  jitchol_used=float(self.gp.extra.get("jitchol", 0.0)),
                  var_mode=self.var_mode, variance=self.variance, chunk=self.chunk)
+        if s.is_sum:   # the terms, one row each; the top-level fields above keep their defaults
+            d.update(sum_family=s.terms[0].family, sum_kinds=np.array([str(t.kind) for t in s.terms]),
+                     sum_weights=np.asarray(s.weights, dtype=np.float64),
+                     sum_params=np.array([[t.l_df, t.l_cf, t.ratio, t.var_t, t.l_t] for t in s.terms],
+                                         dtype=np.float64))
         if with_factor:
             d["W"] = _to_numpy(self.gp.W)
             d["alpha"] = _to_numpy(self.gp.alpha)
@@ -327,6 +343,12 @@ class Krig:
         if fam == "ard":
             spec = E.KernelSpec(family="ard", variances=tuple(z["variances"].tolist()),
                                 lengthscales=tuple(tuple(r) for r in z["lengthscales"].tolist()))
+        elif fam == "vector_sum":
+            tf = str(z["sum_family"])
+            terms = tuple(E.KernelSpec(family=tf, kind=str(kd), l_df=float(p[0]), l_cf=float(p[1]), ratio=float(p[2]),
+                                       var_t=float(p[3]), l_t=float(p[4]))
+                          for kd, p in zip(z["sum_kinds"].tolist(), z["sum_params"]))
+            spec = E.KernelSpec(family="vector_sum", terms=terms, weights=tuple(z["sum_weights"].tolist()))
         else:
             st = dict(var_t=float(z["var_t"]), l_t=float(z["l_t"])) if "var_t" in z.files else {}
             spec = E.KernelSpec(family=fam, kind=str(z["kind"]), l_df=float(z["l_df"]), l_cf=float(z["l_cf"]),
@@ -504,8 +526,13 @@ def kriging(st, et, lalim=(0, 0), lolim=(0, 0), sample_step=5, skip=5, nKernels=
 
     kernelType 1: scalar ARD RBF on (T, Y, X), one model per component (v, u);
     2 / 3 / 4: Kt(var_t, l_t) × div-free / curl-free / mixed vector kernel on (T, Y, X) with
-    obs = [v; u] (krig.py:392-404; hyper 'temporal': False → spatial kernel on (Y, X)).  nKernels > 1 sums nKernels identical ARD terms (krig.py:405-407;
-    ≤ 2 supported).  Hyperparameters come from `hyper` (no optimisation here).
+    obs = [v; u] (krig.py:392-404; hyper 'temporal': False → spatial kernel on (Y, X)).
+    nKernels > 1 sums nKernels terms (krig.py:405-407): for kernelType 1 identical ARD terms (≤ 2
+    supported); for kernelType 2 / 3 / 4 min(nKernels, 3) vector terms of that kind, one per flow
+    scale (engine family 'vector_sum'), where hyper's l_df, l_cf, ratio, variance (the terms'
+    weights), var_t and l_t may be scalars (repeated) or per-term sequences; a spatio-temporal
+    term's amplitude is its var_t, so its weight defaults to 1.  nKernels = 1 is the one-term model
+    and its files, unchanged.  Hyperparameters come from `hyper` (no optimisation here).
     Writes output+'.npz' (the .mat of krig.py:417) and the model files; returns the models.
     """
     if tracks is None:
@@ -532,7 +559,21 @@ def kriging(st, et, lalim=(0, 0), lolim=(0, 0), sample_step=5, skip=5, nKernels=
         obs_all = np.concatenate([d["vo"], d["uo"]], 0)
         obst = np.concatenate([d["vt"], d["ut"]], 0)
         ratio = h["ratio"] if h["ratio"] is not None else {"df": 1.0, "cf": 0.0, "mixed": 0.5}[kind]
-        if h["temporal"]:
+        nk = min(int(nKernels), E.N.SUM_MAX_TERMS)
+        if nk > 1:
+            def per_term(v):
+                v = list(v) if np.ndim(v) else [v] * nk
+                if len(v) != nk:
+                    raise ValueError(f"a per-term hyperparameter needs {nk} values, got {len(v)}")
+                return [float(a) for a in v]
+            fam = "vector_st" if h["temporal"] else "vector2d"
+            cols = [per_term(h[n]) for n in ("l_df", "l_cf", "var_t", "l_t")] + [per_term(ratio)]
+            terms = tuple(E.KernelSpec(family=fam, kind=kind, l_df=a, l_cf=b, ratio=r, var_t=vt, l_t=lt)
+                          for a, b, vt, lt, r in zip(*cols))
+            spec = E.KernelSpec(family="vector_sum", terms=terms, weights=tuple(per_term(h["variance"])))
+            k = Krig(spec, noise=h["noise"], var_mode="gpy", device=device).fit(
+                X if h["temporal"] else X[:, 1:3], obs_all[:, 0])
+        elif h["temporal"]:
             spec = E.KernelSpec(family="vector_st", kind=kind, l_df=h["l_df"], l_cf=h["l_cf"], ratio=ratio,
                                 var_t=h["var_t"], l_t=h["l_t"])
             k = Krig(spec, noise=h["noise"], var_mode="gpy", device=device).fit(X, obs_all[:, 0])
@@ -562,7 +603,7 @@ def runRestarts(fname, nres=10, nKernels=2, device=None, seed=0):
     model.save(filename)
     print("Optimized Hyperparameters =================================================")
     names = E.param_names(model.spec)
-    for nm, a, b in zip(names, hyp_old, hyp):
+    for nm, a, b in zip(names, hyp_old, hyp):   # a kernel sum: weight_t, l_df_t, … per term, as krig.py:459-466
         print(f"{nm} = {a}   :   {b}")
     print("===========================================================================")
     print("End of script, time : " + str(time.time() - t0))

@@ -60,6 +60,9 @@ extern "C" {
 #define GP2D_FAMILY_VECTOR_ST 2  /* spatio-temporal product Kt(t) × vector2d(y, x) on (T, Y, X) points:
                                     var[0]·exp(−Δt²/(2·ls[0][0]²)) times the 2×2 block of `kind`
                                     (scratch.py:506-508 kt * nonDivK; myKernel.py:337-360 Kt)    */
+#define GP2D_FAMILY_VECTOR_SUM 3 /* Σ_t w_t·K(term t): a header descriptor followed by its terms (below);
+                                    the reference's k = k2 + k2 + … (krig.py:405-407), one term per flow scale */
+#define GP2D_SUM_MAX_TERMS 3
 
 /* vector2d kinds — the reference's divFree flag (GP_scripts.py:57-69) */
 #define GP2D_KIND_SCALAR   0     /* divFree=0: scalar SE broadcast into the 2×2 block  */
@@ -83,6 +86,24 @@ typedef struct gp2d_kernel {
     double  var[2];      /* ARD: term variances; VECTOR_ST: var[0] = temporal variance */
     double  ls[2][3];    /* ARD: term length scales per dimension; VECTOR_ST: ls[0][0] = ℓ_t */
 } gp2d_kernel_t;
+
+/* A sum of vector kernels (GP2D_FAMILY_VECTOR_SUM).  Where an entry takes `const gp2d_kernel_t* k`
+ * and k[0].family == GP2D_FAMILY_VECTOR_SUM, k points to an ARRAY of 1 + T descriptors:
+ *   k[0]       the header: nterms = T (1..GP2D_SUM_MAX_TERMS), ls[0][t] = the weight w_t > 0 of term t;
+ *              every other header field is ignored;
+ *   k[1..T]    the terms: all GP2D_FAMILY_VECTOR2D or all GP2D_FAMILY_VECTOR_ST (kinds may differ);
+ *              no ARD term, no nested sum.
+ * The covariance is Σ_t w_t·K(term t); diag_add and the noise are added once, not per term.  With
+ * y = Σ_t f_t + ε, cov(f_t(g), y) = w_t·K_t(g, X): a predict from the sum's fit (W, alpha) with the
+ * one-term sum (w_t, term t) as its kernel is the posterior of term t's contribution alone.
+ * Accepted by gp2d_block_dim (2), gp2d_kernel_diag (Σ w_t·diag_t), gp2d_assemble (every `symmetric`
+ * mode), gp2d_assemble_cols, gp2d_predict, gp2d_field_prior_var (Σ w_t·var_t), gp2d_predict_field
+ * (every term non-scalar; exact zeros only where the field vanishes in every term) and the four
+ * gradient entries.  Gradient order: per term t (weight_t, then the term's own entries in its
+ * family's order without noise: l_df, l_cf, ratio[, var_t, l_t]), then noise (gp2d_lml_grad only);
+ * ∂/∂w_t = Σ weights ⊙ K_t.  gp2d_predict_grad, gp2d_grad_prior_cov, gp2d_predict_cov and every
+ * ozaki entry that takes a kernel refuse a sum on the host (the int8 engine has no K* instantiation,
+ * scale bound or fitted error model for sums).                                                    */
 
 /* ---- sizes ------------------------------------------------------------------- */
 int     gp2d_abi_version(void);
