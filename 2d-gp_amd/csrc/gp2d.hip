@@ -11,6 +11,7 @@
 #include "gemm_f64.hpp"
 #include "factor.hpp"
 #include "predict.hpp"
+#include "trend.hpp"
 #include "fields.hpp"
 #include "grad.hpp"
 #include "postcov.hpp"
@@ -1110,6 +1111,52 @@ static GemmParams wk_gemm_params(const double* W, int64_t ldw, int64_t n, const 
   return p;
 }
 
+// A trend fit's share of a chunked predict (trend.hpp): the basis, the fit's trend block, whether the
+// columns are velocity components (h* = the basis at the target; only if with_basis) or share the
+// constant hc (a derived field's, or zeros), and the target layout.
+struct TrendPredict {
+  int order;
+  TrendBasis basis;
+  const double* block;
+  int with_basis, velocity, pdim;
+  TrendH hc;
+};
+
+// h* of a derived field: h_δ = (0,0,1,0,0,1)/s, h_ζ = (0,0,0,−1,1,0)/s at order 1, zero at order 0
+static TrendH trend_field_h(const TrendPredict& t, int field) {
+  TrendH h{};
+  if (t.with_basis && t.order == 1) {
+    if (field == GP2D_FIELD_DIVERGENCE) { h.v[2] = t.basis.is; h.v[5] = t.basis.is; }
+    else { h.v[3] = -t.basis.is; h.v[4] = t.basis.is; }
+  }
+  return h;
+}
+
+// mean_part_multi_kernel in place of mean_part_kernel: right-hand side 0 = α′, then B0's columns
+static int launch_mean_partials_trend(const double* B, int64_t ncols, int64_t n, const TrendPredict& t, double* pm,
+                                      hipStream_t s) {
+  const int64_t nseg = predict_segments(n);
+  const dim3 grid((unsigned)((ncols + 255) / 256), (unsigned)nseg);
+  const double* rhs = t.block + TB_RHS;
+  if (t.order == 0) mean_part_multi_kernel<3><<<grid, 256, 0, s>>>(B, ncols, ncols, rhs, nseg, pm);
+  else mean_part_multi_kernel<TREND_QMAX + 1><<<grid, 256, 0, s>>>(B, ncols, ncols, rhs, nseg, pm);
+  return check_launch("mean_part_multi_kernel");
+}
+
+static int launch_finalize_trend(const Finalize& f, const TrendPredict& t, const double* xg, hipStream_t s) {
+  const unsigned grid = (unsigned)((f.ncols + 63) / 64);
+  if (t.order == 0)
+    predict_trend_finalize_kernel<2><<<grid, 64, 0, s>>>(f.pm, f.P, f.nmseg, f.ncols, f.cp, f.cv, f.c0, f.m, f.prior,
+                                                         f.add, f.clip, f.compute_var, f.mean, f.var, xg, t.pdim,
+                                                         t.basis, t.velocity, t.hc, t.block);
+  else
+    predict_trend_finalize_kernel<TREND_QMAX><<<grid, 64, 0, s>>>(f.pm, f.P, f.nmseg, f.ncols, f.cp, f.cv, f.c0, f.m,
+                                                                  f.prior, f.add, f.clip, f.compute_var, f.mean,
+                                                                  f.var, xg, t.pdim, t.basis, t.velocity, t.hc,
+                                                                  t.block);
+  return check_launch("predict_trend_finalize_kernel");
+}
+
 // What differs between the chunked predicts: columns per target, the variance's terms, whether
 // the product goes to the timing hooks, and the chunk's cross-covariance — assemble(the chunk's
 // targets, valid count, padded count, out) writes K*ᵀ (n × bd·cp: rows = training components,
@@ -1124,6 +1171,7 @@ struct ChunkedPredict {
   std::function<int(const double* xg, int64_t cv, int64_t cp, double* Ks)> assemble;
   bool gram = false;
   GradPrior prior4{};
+  const TrendPredict* trend = nullptr;   // a trend fit's predict: the multi-right-hand-side mean pass and finalize
 };
 
 // One chunked predict over the m targets (dim coordinates each): per chunk assemble, mean partials,
@@ -1139,7 +1187,8 @@ static int predict_chunks(const ChunkedPredict& v, const double* W, int64_t n, i
     const int64_t cp = round_up(cv, std::max<int64_t>(PT_TILE, GBN / v.bd));   // whole point tiles (grad: 16-groups)
     const int64_t ncols = v.bd * cp;
     GP2D_CHECK(v.assemble(xg + c0 * dim, cv, cp, Ks));
-    GP2D_CHECK(launch_mean_partials(Ks, ncols, n, alpha, pm, s));
+    if (v.trend) GP2D_CHECK(launch_mean_partials_trend(Ks, ncols, n, *v.trend, pm, s));
+    else GP2D_CHECK(launch_mean_partials(Ks, ncols, n, alpha, pm, s));
     if (compute_var) {
       GemmParams p = wk_gemm_params(W, ldw, n, Ks, ncols);
       p.P = P; p.ldp = v.gram ? GRAD_NPAIR * cp : ncols;
@@ -1151,6 +1200,9 @@ static int predict_chunks(const ChunkedPredict& v, const double* W, int64_t n, i
       grad_finalize_kernel<<<(unsigned)((cv + 63) / 64), 64, 0, s>>>(pm, P, nseg, cp, cv, c0, v.prior4, compute_var,
                                                                       mean, var);
       GP2D_CHECK(check_launch("grad_finalize_kernel"));
+    } else if (v.trend) {   // xg: all m targets; the kernel indexes them by c0 + its column
+      GP2D_CHECK(launch_finalize_trend({pm, nseg, P, nseg, ncols, cp, cv, c0, m, v.prior, v.add, v.clip, compute_var,
+                                        mean, var, nullptr}, *v.trend, xg, s));
     } else {
       GP2D_CHECK(launch_finalize({pm, nseg, P, nseg, ncols, cp, cv, c0, m, v.prior, v.add, v.clip, compute_var, mean,
                                   var, nullptr}, s));
@@ -1163,26 +1215,50 @@ static int predict_chunks(const ChunkedPredict& v, const double* W, int64_t n, i
 static int predict_chunks(const ChunkedPredict& v, const double* W, int64_t n, int64_t ldw, const double* alpha,
                           int64_t ntr, const double* xg, int dim, int64_t m, int compute_var, double* mean,
                           double* var, int64_t chunk, void* work, hipStream_t s) {
-  const auto [Ks, pm, P] = PredictWork(n, v.bd * chunk).at(work);
+  const auto [Ks, pm, P] = v.trend ? PredictTrendWork(n, v.bd * chunk, v.trend->order).at(work)
+                                   : PredictWork(n, v.bd * chunk).at(work);
   return predict_chunks(v, W, n, ldw, alpha, ntr, xg, dim, m, compute_var, mean, var, chunk, Ks, pm, P, s);
+}
+
+// ---- the trend descriptor's checks (every trend entry, before any launch) and its basis
+static int validate_trend(const gp2d_trend_t* t, const double* block, const char* entry) {
+  const std::string e(entry);
+  GP2D_REQUIRE(t != nullptr, e + ": trend is NULL");
+  GP2D_REQUIRE(t->order == 0 || t->order == 1, e + ": trend order must be 0 (constant) or 1 (linear)");
+  GP2D_REQUIRE(std::isfinite(t->scale) && t->scale > 0.0, e + ": trend scale must be finite and > 0");
+  GP2D_REQUIRE(std::isfinite(t->centre[0]) && std::isfinite(t->centre[1]), e + ": trend centre must be finite");
+  GP2D_REQUIRE(block != nullptr, e + ": block is NULL");
+  GP2D_REQUIRE(reinterpret_cast<uintptr_t>(block) % 64 == 0, e + ": block must be 64-byte aligned");
+  return 0;
+}
+static TrendBasis trend_basis_of(const gp2d_trend_t* t) { return {t->centre[0], t->centre[1], 1.0 / t->scale}; }
+
+int gp2d_trend_coefficients(int order) { return (order == 0 || order == 1) ? trend_q(order) : -2; }
+size_t gp2d_trend_block_doubles(int64_t n) { return TrendBlock(n).doubles; }
+size_t gp2d_predict_trend_workspace(int64_t n, int64_t chunk, int bd, int order) {
+  return PredictTrendWork(n, predict_sized_cols(chunk, bd), order == 0 ? 0 : 1).total;
 }
 
 size_t gp2d_predict_workspace(int64_t n, int64_t chunk, int bd) {
   return PredictWork(n, predict_sized_cols(chunk, bd)).total;
 }
 
-int gp2d_predict(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
-                 int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, int var_mode, double noise,
-                 int compute_var, double* mean, double* var, int64_t chunk, void* work, size_t work_bytes,
-                 void* stream) {
+// gp2d_predict, and with tp gp2d_predict_trend (tp's column kind and pdim are set here)
+static int predict_impl(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
+                        int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, int var_mode,
+                        double noise, int compute_var, double* mean, double* var, int64_t chunk, void* work,
+                        size_t work_bytes, void* stream, TrendPredict* tp) {
   GP2D_CHECK(validate_kernel(k));
   const int bd = gp2d_block_dim(k);
+  GP2D_REQUIRE(tp == nullptr || bd == 2, "predict_trend: k must be a vector kernel (two components per point)");
   GP2D_REQUIRE(n == bd * ntr_pad, "predict: n must equal block_dim × ntr_pad");
   GP2D_REQUIRE(n % NB == 0, "predict: n must be a multiple of 128");
-  GP2D_REQUIRE(ld_even(ldw, n), "predict: ldw must be >= n and even");
+  GP2D_REQUIRE(ld_even(ldw, n), tp ? "predict_trend: wld must be >= n and even" : "predict: ldw must be >= n and even");
   GP2D_REQUIRE(chunk > 0 && chunk % PT_TILE == 0, "predict: chunk must be a positive multiple of 64");
   GP2D_REQUIRE(bd * chunk % GBN == 0, "predict: block_dim × chunk must be a multiple of 128");
-  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_predict_workspace(n, chunk, bd), "predict: workspace too small");
+  GP2D_REQUIRE(work != nullptr && work_bytes >= (tp ? gp2d_predict_trend_workspace(n, chunk, bd, tp->order)
+                                                    : gp2d_predict_workspace(n, chunk, bd)),
+               "predict: workspace too small");
   GP2D_REQUIRE(var_mode >= 0 && var_mode <= 2, "predict: bad var_mode");
   if (m <= 0) return 0;
   GP2D_REQUIRE(aligned16(W), "predict: W must be 16-byte aligned");
@@ -1196,7 +1272,21 @@ int gp2d_predict(const double* W, int64_t n, int64_t ldw, const double* alpha, c
   v.assemble = [=](const double* xc, int64_t cv, int64_t cp, double* Ks) {
     return assemble_impl(xtr, ntr, ntr_pad, xc, cv, cp, k, 0.0, 0, Ks, bd * cp, s);
   };
+  if (tp) {
+    tp->velocity = tp->with_basis;   // one term of a sum: h* = 0 for every column
+    tp->hc = TrendH{};
+    tp->pdim = point_dim(k);
+    v.trend = tp;
+  }
   return predict_chunks(v, W, n, ldw, alpha, ntr, xg, point_dim(k), m, compute_var, mean, var, chunk, work, s);
+}
+
+int gp2d_predict(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
+                 int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, int var_mode, double noise,
+                 int compute_var, double* mean, double* var, int64_t chunk, void* work, size_t work_bytes,
+                 void* stream) {
+  return predict_impl(W, n, ldw, alpha, xtr, ntr, ntr_pad, xg, m, k, var_mode, noise, compute_var, mean, var, chunk,
+                      work, work_bytes, stream, nullptr);
 }
 
 // ------------------------------------------------------- PREDICT (derived fields)
@@ -1231,10 +1321,11 @@ double gp2d_field_prior_var(const gp2d_kernel_t* k, int field) {
 
 size_t gp2d_predict_field_workspace(int64_t n, int64_t chunk) { return gp2d_predict_workspace(n, chunk, 1); }
 
-int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
-                       int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, int field,
-                       int compute_var, double* mean, double* var, int64_t chunk, void* work, size_t work_bytes,
-                       void* stream) {
+// gp2d_predict_field, and with tp gp2d_predict_field_trend (tp's h* and pdim are set here)
+static int predict_field_impl(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr,
+                              int64_t ntr, int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k,
+                              int field, int compute_var, double* mean, double* var, int64_t chunk, void* work,
+                              size_t work_bytes, void* stream, TrendPredict* tp) {
   GP2D_CHECK(validate_kernel(k));
   GP2D_REQUIRE(field_kernel_ok(k), "predict_field: div-free, curl-free or mixed vector kernels only");
   GP2D_REQUIRE(field == GP2D_FIELD_DIVERGENCE || field == GP2D_FIELD_VORTICITY,
@@ -1242,9 +1333,11 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
   GP2D_REQUIRE(n == 2 * ntr_pad, "predict_field: n must equal 2 × ntr_pad");
   GP2D_REQUIRE(n % NB == 0 && n > 0, "predict_field: n must be a positive multiple of 128");
   GP2D_REQUIRE(ntr >= 0 && ntr <= ntr_pad, "predict_field: bad point count");
-  GP2D_REQUIRE(ld_even(ldw, n), "predict_field: ldw must be >= n and even");
+  GP2D_REQUIRE(ld_even(ldw, n),
+               tp ? "predict_field_trend: wld must be >= n and even" : "predict_field: ldw must be >= n and even");
   GP2D_REQUIRE(chunk > 0 && chunk % GBN == 0, "predict_field: chunk must be a positive multiple of 128");
-  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_predict_field_workspace(n, chunk),
+  GP2D_REQUIRE(work != nullptr && work_bytes >= (tp ? gp2d_predict_trend_workspace(n, chunk, 1, tp->order)
+                                                    : gp2d_predict_field_workspace(n, chunk)),
                "predict_field: workspace too small");
   if (m <= 0) return 0;
   GP2D_REQUIRE(aligned16(W), "predict_field: W must be 16-byte aligned");
@@ -1254,7 +1347,7 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
     vanishes = true;
     for (int t = 0; t < k->nterms; ++t) vanishes = vanishes && field_vanishes(sum_term(k, t), field);
   }
-  if (vanishes) {
+  if (vanishes && tp == nullptr) {
     // div-free flow has no divergence, curl-free flow no vorticity: exact zeros, no GEMM
     if (hipMemsetAsync(mean, 0, sizeof(double) * (size_t)m, s) != hipSuccess ||
         (compute_var && hipMemsetAsync(var, 0, sizeof(double) * (size_t)m, s) != hipSuccess)) {
@@ -1274,12 +1367,93 @@ int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* al
       return launch_cross_cov(fe, xtr, ntr, ntr_pad, xc, cv, cp, Ks, cp, 0, cp, s);
     };
   } else {
-    const FieldEntry fe = make_field_entry(k, field);
+    FieldEntry fe = make_field_entry(k, field);
+    if (vanishes) fe.il2 = fe.w4 = 0.0;   // (a trend predict) exact zeros whatever the unused length scale holds
     v.assemble = [=](const double* xc, int64_t cv, int64_t cp, double* Ks) {
       return launch_cross_cov(fe, xtr, ntr, ntr_pad, xc, cv, cp, Ks, cp, 0, cp, s);
     };
   }
+  if (tp) {   // a field that vanishes by kind keeps the general path: exact-zero K*, the trend's terms remain
+    tp->velocity = 0;
+    tp->hc = trend_field_h(*tp, field);
+    tp->pdim = point_dim(k);
+    v.trend = tp;
+  }
   return predict_chunks(v, W, n, ldw, alpha, ntr, xg, point_dim(k), m, compute_var, mean, var, chunk, work, s);
+}
+
+int gp2d_predict_field(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
+                       int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, int field,
+                       int compute_var, double* mean, double* var, int64_t chunk, void* work, size_t work_bytes,
+                       void* stream) {
+  return predict_field_impl(W, n, ldw, alpha, xtr, ntr, ntr_pad, xg, m, k, field, compute_var, mean, var, chunk, work,
+                            work_bytes, stream, nullptr);
+}
+
+// ------------------------------------------------------- TREND (background flow, trend.hpp)
+size_t gp2d_trend_workspace(int64_t n, int order) { (void)order; return TrendFitWork(n).total; }
+
+int gp2d_trend_fit(const double* W, int64_t n, int64_t wld, const double* y, const double* xtr, int64_t ntr,
+                   int64_t ntr_pad, int dim, const gp2d_trend_t* trend, double* alpha_out, double* block_out,
+                   void* work, size_t work_bytes, void* stream) {
+  GP2D_CHECK(validate_trend(trend, block_out, "trend_fit"));
+  GP2D_REQUIRE(W && y && xtr && alpha_out, "trend_fit: NULL argument");
+  GP2D_REQUIRE(n % NB == 0 && n > 0, "trend_fit: n must be a positive multiple of 128");
+  GP2D_REQUIRE(n == 2 * ntr_pad && ntr_pad % PT_TILE == 0, "trend_fit: n must equal 2 × ntr_pad");
+  GP2D_REQUIRE(ntr >= 1 && ntr <= ntr_pad, "trend_fit: bad point count");
+  GP2D_REQUIRE(dim == 2 || dim == 3, "trend_fit: dim must be 2 or 3");
+  GP2D_REQUIRE(wld >= n, "trend_fit: wld must be >= n");
+  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_trend_workspace(n, trend->order),
+               "trend_fit: workspace too small");
+  hipStream_t s = S(stream);
+  const auto [Y, Z, part] = TrendFitWork(n).at(work);
+  const TrendBasis tb = trend_basis_of(trend);
+  const int64_t nseg = n / NB;
+  const unsigned rows = (unsigned)((n + 255) / 256);
+  const dim3 tgrid(rows, (unsigned)nseg);
+  if (trend->order == 0) {
+    trend_rhs_kernel<2><<<rows, 256, 0, s>>>(y, xtr, ntr, ntr_pad, dim, tb, Y);
+    GP2D_CHECK(check_launch("trend_rhs_kernel"));
+    trmv_n_lower_multi_kernel<3><<<(unsigned)((n + 3) / 4), 256, 0, s>>>(W, n, wld, Y, Z);
+    GP2D_CHECK(check_launch("trmv_n_lower_multi_kernel"));
+    trend_solve_kernel<2><<<1, 256, 0, s>>>(Z, n, block_out);
+    GP2D_CHECK(check_launch("trend_solve_kernel"));
+    trmv_t_lower_multi_part_kernel<3><<<tgrid, 256, 0, s>>>(W, n, wld, Z, block_out, part);
+  } else {
+    trend_rhs_kernel<TREND_QMAX><<<rows, 256, 0, s>>>(y, xtr, ntr, ntr_pad, dim, tb, Y);
+    GP2D_CHECK(check_launch("trend_rhs_kernel"));
+    trmv_n_lower_multi_kernel<TREND_QMAX + 1><<<(unsigned)((n + 3) / 4), 256, 0, s>>>(W, n, wld, Y, Z);
+    GP2D_CHECK(check_launch("trmv_n_lower_multi_kernel"));
+    trend_solve_kernel<TREND_QMAX><<<1, 256, 0, s>>>(Z, n, block_out);
+    GP2D_CHECK(check_launch("trend_solve_kernel"));
+    trmv_t_lower_multi_part_kernel<TREND_QMAX + 1><<<tgrid, 256, 0, s>>>(W, n, wld, Z, block_out, part);
+  }
+  GP2D_CHECK(check_launch("trmv_t_lower_multi_part_kernel"));
+  trend_sum_kernel<<<(unsigned)((n * TREND_RHS + 255) / 256), 256, 0, s>>>(part, nseg, n, alpha_out,
+                                                                           block_out + TB_RHS);
+  return check_launch("trend_sum_kernel");
+}
+
+int gp2d_predict_trend(const double* W, int64_t n, int64_t wld, const double* alpha, const double* xtr, int64_t ntr,
+                       int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k, int var_mode,
+                       double noise, int compute_var, double* mean, double* var, int64_t chunk, void* work,
+                       size_t work_bytes, void* stream, const gp2d_trend_t* trend, const double* block,
+                       int with_basis) {
+  GP2D_CHECK(validate_trend(trend, block, "predict_trend"));
+  TrendPredict tp{trend->order, trend_basis_of(trend), block, with_basis != 0, 0, 2, TrendH{}};
+  return predict_impl(W, n, wld, alpha, xtr, ntr, ntr_pad, xg, m, k, var_mode, noise, compute_var, mean, var, chunk,
+                      work, work_bytes, stream, &tp);
+}
+
+int gp2d_predict_field_trend(const double* W, int64_t n, int64_t wld, const double* alpha, const double* xtr,
+                             int64_t ntr, int64_t ntr_pad, const double* xg, int64_t m, const gp2d_kernel_t* k,
+                             int field, int compute_var, double* mean, double* var, int64_t chunk, void* work,
+                             size_t work_bytes, void* stream, const gp2d_trend_t* trend, const double* block,
+                             int with_basis) {
+  GP2D_CHECK(validate_trend(trend, block, "predict_field_trend"));
+  TrendPredict tp{trend->order, trend_basis_of(trend), block, with_basis != 0, 0, 2, TrendH{}};
+  return predict_field_impl(W, n, wld, alpha, xtr, ntr, ntr_pad, xg, m, k, field, compute_var, mean, var, chunk, work,
+                            work_bytes, stream, &tp);
 }
 
 // ------------------------------------------------------- PREDICT (velocity gradient tensor)
@@ -1886,6 +2060,19 @@ int gp2d_lml(const double* W, int64_t n, int64_t ldw, const double* alpha, const
   return check_launch("lml_terms_kernel");
 }
 
+int gp2d_lml_trend(const double* W, int64_t n, int64_t wld, const double* alpha, const double* y, int64_t nobs,
+                   const gp2d_trend_t* trend, const double* block, double* lml_dev, void* stream) {
+  GP2D_CHECK(validate_trend(trend, block, "lml_trend"));
+  GP2D_REQUIRE(W && alpha && y && lml_dev, "lml_trend: NULL argument");
+  GP2D_REQUIRE(n > 0 && nobs >= 0 && nobs <= n, "lml_trend: bad sizes");
+  GP2D_REQUIRE(wld >= n, "lml_trend: wld must be >= n");
+  hipStream_t s = S(stream);
+  lml_terms_kernel<<<1, 256, 0, s>>>(W, n, wld, alpha, y, nobs, lml_dev);
+  GP2D_CHECK(check_launch("lml_terms_kernel"));
+  lml_trend_terms_kernel<<<1, 64, 0, s>>>(lml_dev, block, trend_q(trend->order));
+  return check_launch("lml_trend_terms_kernel");
+}
+
 int gp2d_lml_grad_count(const gp2d_kernel_t* k) {
   if (validate_kernel(k) != 0) return -2;
   if (is_sum_family(k))   // per term its weight and its own entries without noise, then noise
@@ -1972,16 +2159,20 @@ extern "C" {
 
 size_t gp2d_lml_grad_workspace(int64_t n) { return LmlGradWork(n).total; }
 
-int gp2d_lml_grad(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
-                  int64_t ntr_pad, const gp2d_kernel_t* k, double* grad_dev, void* work, size_t work_bytes,
-                  void* stream) {
+// gp2d_lml_grad, and with a trend (order, block) gp2d_lml_grad_trend: the rank-q update of C between
+// the product and the pair loop
+static int lml_grad_impl(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
+                         int64_t ntr_pad, const gp2d_kernel_t* k, double* grad_dev, void* work, size_t work_bytes,
+                         void* stream, int order, const double* block) {
   GP2D_CHECK(validate_kernel(k));
   GP2D_REQUIRE(W && alpha && xtr && grad_dev, "lml_grad: NULL argument");
   const int bd = gp2d_block_dim(k);
   GP2D_REQUIRE(n == bd * ntr_pad && ntr_pad % PT_TILE == 0, "lml_grad: n must equal block_dim × ntr_pad");
   GP2D_REQUIRE(n % NB == 0, "lml_grad: n must be a multiple of 128");
   GP2D_REQUIRE(ntr >= 1 && ntr <= ntr_pad, "lml_grad: bad sizes");
-  GP2D_REQUIRE(ld_even(ldw, n), "lml_grad: ldw must be >= n and even");
+  GP2D_REQUIRE(block == nullptr || bd == 2, "lml_grad_trend: k must be a vector kernel (two components per point)");
+  GP2D_REQUIRE(ld_even(ldw, n),
+               block ? "lml_grad_trend: wld must be >= n and even" : "lml_grad: ldw must be >= n and even");
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_lml_grad_workspace(n), "lml_grad: workspace too small");
   GP2D_REQUIRE(aligned16(W), "lml_grad: W must be 16-byte aligned");
   // (the two checks above cover both operands of the TN product below: as A and as B, W is read in
@@ -1996,8 +2187,30 @@ int gp2d_lml_grad(const double* W, int64_t n, int64_t ldw, const double* alpha, 
   p.M = (int)n; p.N = (int)n; p.K = (int)n;
   p.a_upper = 1; p.c_lower = 1;
   GP2D_CHECK((launch_gemm<false, EPI_STORE, true>(p, 1, s)));
+  if (block) {   // C ← K_y⁻¹ − B0·A⁻¹·B0ᵀ on the stored triangle
+    const dim3 grid((unsigned)n, (unsigned)((n + 255) / 256));
+    if (order == 0) trend_rank_update_kernel<2><<<grid, 256, 0, s>>>(C, n, block);
+    else trend_rank_update_kernel<TREND_QMAX><<<grid, 256, 0, s>>>(C, n, block);
+    GP2D_CHECK(check_launch("trend_rank_update_kernel"));
+  }
   return launch_pair_grad(k, xtr, ntr, xtr, ntr, ntr_pad, TraceWeights{C, n, alpha, ntr_pad}, partial, 0.5, true,
                           grad_dev, s);
+}
+
+int gp2d_lml_grad(const double* W, int64_t n, int64_t ldw, const double* alpha, const double* xtr, int64_t ntr,
+                  int64_t ntr_pad, const gp2d_kernel_t* k, double* grad_dev, void* work, size_t work_bytes,
+                  void* stream) {
+  return lml_grad_impl(W, n, ldw, alpha, xtr, ntr, ntr_pad, k, grad_dev, work, work_bytes, stream, 0, nullptr);
+}
+
+size_t gp2d_lml_grad_trend_workspace(int64_t n) { return gp2d_lml_grad_workspace(n); }
+
+int gp2d_lml_grad_trend(const double* W, int64_t n, int64_t wld, const double* alpha, const double* xtr, int64_t ntr,
+                        int64_t ntr_pad, const gp2d_kernel_t* k, const gp2d_trend_t* trend, const double* block,
+                        double* grad_dev, void* work, size_t work_bytes, void* stream) {
+  GP2D_CHECK(validate_trend(trend, block, "lml_grad_trend"));
+  return lml_grad_impl(W, n, wld, alpha, xtr, ntr, ntr_pad, k, grad_dev, work, work_bytes, stream, trend->order,
+                       block);
 }
 
 size_t gp2d_kernel_grad_workspace(int64_t na, int64_t nb) { return KernelGradWork(na, nb).total; }

@@ -1,11 +1,12 @@
-// predict_host.hpp — the three workspace layouts of the FP64 predicts (gp2d_predict and
-// gp2d_predict_field; gp2d_predict_grad; gp2d_predict_cov), as byte-offset tables.  gp2d.hip takes every FP64 predict
+// predict_host.hpp — the workspace layouts of the FP64 predicts (gp2d_predict and
+// gp2d_predict_field; gp2d_predict_grad; gp2d_predict_cov; the trend fit, block and predicts), as byte-offset tables.  gp2d.hip takes every FP64 predict
 // workspace size it reports and every pointer it carves from here; nothing else knows the layouts
 // (the kernels in predict.hpp, gemm_f64.hpp and postcov.hpp get plain pointers).
 #pragma once
 #include "factor_host.hpp"
 #include "gemm_f64.hpp"
 #include "predict.hpp"
+#include "trend.hpp"
 
 namespace gp2d {
 
@@ -51,6 +52,72 @@ static_assert(predict_work_ok(128, 128) && predict_work_ok(256, 256) && predict_
                   predict_sized_cols(8192, 2) == 16384 && predict_sized_cols(64, 1) == 128 &&
                   predict_sized_cols(0, 2) == 128 && predict_sized_cols(100, 2) == 256,
               "predict workspace: regions out of order, overlapping or misaligned");
+
+// The trend block gp2d_trend_fit writes and the trend predicts and likelihoods read (trend.hpp's
+// TB_* offsets, in doubles): β̂ (q, padded to 8) | A⁻¹ (q × q at row stride TREND_QMAX) | log|A| |
+// status (0, or the 1-based order of A's failed pivot) | the right-hand sides, n rows of TREND_RHS
+// doubles: [α′_i, B0[i][0..q), 0…].  The table starts on a 128-byte boundary of the block, so a row
+// is one aligned 64-byte piece when the block itself is 64-byte aligned.
+struct TrendBlock {
+  size_t beta = 0, ainv = 0, logdet = 0, status = 0, rhs = 0, doubles = 0;
+  constexpr explicit TrendBlock(int64_t n) {
+    ainv = beta + 8;
+    logdet = ainv + (size_t)TREND_QMAX * TREND_QMAX;
+    status = logdet + 1;
+    rhs = round_up((int64_t)status + 1, 16);
+    doubles = rhs + (size_t)TREND_RHS * (size_t)(n > 0 ? n : 0);
+  }
+};
+constexpr int trend_q(int order) { return order == 0 ? 2 : TREND_QMAX; }
+static_assert(TrendBlock(0).beta == TB_BETA && TrendBlock(0).ainv == TB_AINV && TrendBlock(0).logdet == TB_LOGDET &&
+                  TrendBlock(0).status == TB_STATUS && TrendBlock(0).rhs == TB_RHS && TrendBlock(0).doubles == 48 &&
+                  TrendBlock(256).doubles == 48 + 8 * 256 && TREND_QMAX + 1 <= TREND_RHS && TREND_QMAX <= 8 &&
+                  TB_RHS % 8 == 0 && trend_q(0) == 2 && trend_q(1) == 6,
+              "trend block: the kernels' offsets and the layout disagree");
+
+// Workspace of gp2d_trend_fit: the table Y = [y | Hᵀ] (n rows of TREND_RHS) | Z = W·Y | the n / 128
+// row segments' partial sums of Wᵀ·[z − Gβ̂ | G] (n rows of TREND_RHS each), sized for one segment more.
+struct TrendFitWork {
+  size_t Y = 0, Z = 0, part = 0, total = 0;
+  constexpr explicit TrendFitWork(int64_t n) {
+    const size_t tab = F64 * (size_t)TREND_RHS * (size_t)(n > 0 ? n : 0);
+    Z = tab;
+    part = 2 * tab;
+    total = part + (size_t)((n > 0 ? n : 0) / NB + 1) * tab;
+  }
+  struct Ptrs { double* Y; double* Z; double* part; };
+  Ptrs at(void* w) const { return {work_at(w, Y), work_at(w, Z), work_at(w, part)}; }
+};
+constexpr bool trend_fit_work_ok(int64_t n) {
+  const TrendFitWork w(n);
+  const size_t tab = F64 * 8 * (size_t)n;
+  return regions_ok({w.Y, w.Z, w.part, w.total}, {tab, tab, (size_t)(n / 128 + 1) * tab}) &&
+         w.total == tab * (size_t)(3 + n / 128);
+}
+static_assert(trend_fit_work_ok(128) && trend_fit_work_ok(256) && trend_fit_work_ok(16384) &&
+                  TrendFitWork(0).total == 0,
+              "trend_fit workspace: regions out of order, overlapping or misaligned");
+
+// Workspace of gp2d_predict_trend and gp2d_predict_field_trend: PredictWork's regions with q + 1
+// sets of mean partials (pm[r][segment][column], right-hand side 0 = α′) in place of one.
+struct PredictTrendWork {
+  size_t Ks = 0, pm = 0, P = 0, total = 0;
+  constexpr PredictTrendWork(int64_t n, int64_t ncols, int order) {
+    pm = F64 * (size_t)n * (size_t)ncols;
+    P = pm + (size_t)(trend_q(order) + 1) * predict_partial_bytes(n, ncols);
+    total = P + predict_partial_bytes(n, ncols);
+  }
+  PredictWork::Ptrs at(void* w) const { return {work_at(w, Ks), work_at(w, pm), work_at(w, P)}; }
+};
+constexpr bool predict_trend_work_ok(int64_t n, int64_t ncols, int order) {
+  const PredictTrendWork w(n, ncols, order);
+  const size_t part = F64 * (size_t)(n / 128 + 1) * (size_t)ncols, q1 = order == 0 ? 3 : 7;
+  return regions_ok({w.Ks, w.pm, w.P, w.total}, {F64 * (size_t)n * (size_t)ncols, q1 * part, part}) &&
+         w.total == PredictWork(n, ncols).total + (q1 - 1) * part;
+}
+static_assert(predict_trend_work_ok(128, 128, 0) && predict_trend_work_ok(256, 256, 1) &&
+                  predict_trend_work_ok(8192, 16384, 1),
+              "predict_trend workspace: regions out of order, overlapping or misaligned");
 
 // Workspace of gp2d_predict_grad: C = cov(observations, ∇f) of a chunk (n × 4·chunk, grad.hpp's
 // column layout) | the mean's partial sums (4·chunk columns) | the Gram partial sums (10 per target

@@ -50,6 +50,9 @@ EXPORTS = (
     "gp2d_dfact_invstep", "gp2d_dfact_zpart", "gp2d_dfact_zsum", "gp2d_dfact_alpha_workspace", "gp2d_dfact_alpha_blocks",
     "gp2d_assemble_cols", "gp2d_copy2d", "gp2d_zero_upper", "gp2d_pack_lower_doubles", "gp2d_pack_lower",
     "gp2d_timing_enable", "gp2d_timing_read", "gp2d_trace_mark", "gp2d_last_error",
+    "gp2d_trend_coefficients", "gp2d_trend_block_doubles", "gp2d_trend_workspace", "gp2d_trend_fit",
+    "gp2d_predict_trend_workspace", "gp2d_predict_trend", "gp2d_predict_field_trend",
+    "gp2d_lml_trend", "gp2d_lml_grad_trend_workspace", "gp2d_lml_grad_trend",
 )
 
 
@@ -75,6 +78,28 @@ class KernelDesc(ctypes.Structure):
     ]
 
 
+class TrendDesc(ctypes.Structure):
+    """gp2d_trend_t: the background flow's basis (order 0 constant, 1 linear; centre, scale)."""
+    _fields_ = [
+        ("order", ctypes.c_int32),
+        ("centre", ctypes.c_double * 2),
+        ("scale", ctypes.c_double),
+    ]
+
+
+TREND_ORDERS = {"constant": 0, "linear": 1}
+# the trend block's layout in doubles (csrc/predict_host.hpp TrendBlock)
+TREND_BETA, TREND_AINV, TREND_AINV_LD, TREND_LOGDET, TREND_STATUS, TREND_RHS, TREND_RHS_LD = 0, 8, 6, 44, 45, 48, 8
+
+
+def trend_desc(order: int, centre, scale: float) -> TrendDesc:
+    t = TrendDesc()
+    t.order = int(order)
+    t.centre[0], t.centre[1] = float(centre[0]), float(centre[1])
+    t.scale = float(scale)
+    return t
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -92,7 +117,21 @@ class _KP(ctypes.c_void_p):
 
 
 
+_TP = ctypes.POINTER(TrendDesc)
+_PREDICT_ARGS = [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _KP, _I, _D, _I, _P, _P, _I64, _P, _SZ, _P]
+_PREDICT_FIELD_ARGS = [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _KP, _I, _I, _P, _P, _I64, _P, _SZ, _P]
+
 _SIGS = {
+    "gp2d_trend_coefficients": (_I, [_I]),
+    "gp2d_trend_block_doubles": (_SZ, [_I64]),
+    "gp2d_trend_workspace": (_SZ, [_I64, _I]),
+    "gp2d_trend_fit": (_I, [_P, _I64, _I64, _P, _P, _I64, _I64, _I, _TP, _P, _P, _P, _SZ, _P]),
+    "gp2d_predict_trend_workspace": (_SZ, [_I64, _I64, _I, _I]),
+    "gp2d_predict_trend": (_I, _PREDICT_ARGS + [_TP, _P, _I]),
+    "gp2d_predict_field_trend": (_I, _PREDICT_FIELD_ARGS + [_TP, _P, _I]),
+    "gp2d_lml_trend": (_I, [_P, _I64, _I64, _P, _P, _I64, _TP, _P, _P, _P]),
+    "gp2d_lml_grad_trend_workspace": (_SZ, [_I64]),
+    "gp2d_lml_grad_trend": (_I, [_P, _I64, _I64, _P, _P, _I64, _I64, _KP, _TP, _P, _P, _P, _SZ, _P]),
     "gp2d_abi_version": (_I, []),
     "gp2d_build_info": (ctypes.c_char_p, []),
     "gp2d_padded_points": (_I64, [_I64]),

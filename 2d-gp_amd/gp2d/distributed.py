@@ -64,6 +64,8 @@ def broadcast_fit(gp: E.GPFit | None, spec: E.KernelSpec, noise: float, x, devic
     and no unpack of an n×n matrix per job.
     comm (optional dict): bytes this rank sends / receives and the collectives' HIP-event times
     are appended under 'bcast' (collect with comm_summary)."""
+    if gp is not None:   # the trend block does not travel with the factor
+        E.refuse_trend(gp, "broadcast_fit")
     ws, rank = world()
     if _solo(ws):
         if error is not None:
@@ -242,11 +244,13 @@ def packed_blocks(n: int):
 
 
 def fit_sharded(spec: E.KernelSpec, x, y, noise: float, device, mode: str = "bcast", jitter: float = 0.0,
-                variance: str = "f64", check: bool = True):
+                variance: str = "f64", check: bool = True, trend: str | None = None):
     """mode 'bcast': rank 0 fits, factor broadcast over RCCL; 'replicate': every rank
     fits redundantly (no communication).  With variance='ozaki' every rank derives its
     INT8 residue planes from the broadcast factor locally (no extra traffic).  check=False as
-    in engine.fit (replicate mode; in bcast mode rank 0 checks before broadcasting)."""
+    in engine.fit (replicate mode; in bcast mode rank 0 checks before broadcasting).  trend: refused
+    (a background flow is fitted by engine.fit on one device)."""
+    E.refuse_trend(trend, "fit_sharded", ": use engine.fit(trend=) on one device")
     ws, rank = world()
     if _solo(ws) or mode == "replicate":
         return E.fit(spec, x, y, noise, jitter=jitter, device=device, variance=variance, check=check)
@@ -287,7 +291,7 @@ def _owned_blocks(nsb: int, ws: int, r: int):
 
 def fit_distributed(spec: E.KernelSpec, x, y, noise: float, device=None, variance: str = "ozaki",
                     jitter: float = 0.0, lookahead: bool = True, stats: dict | None = None,
-                    emulate: tuple | None = None, comm: dict | None = None) -> E.GPFit:
+                    emulate: tuple | None = None, comm: dict | None = None, trend: str | None = None) -> E.GPFit:
     """ONE job's fit spread over all ranks (the config-D single job: /root/reference/krig.py:541-557
     predicts one model's large grid): every rank assembles K_y, then a 1-D block-cyclic POTRF
     fused with the right-looking TRTRI (include/gp2d.h gp2d_dfact_*) — rank s mod P factors
@@ -312,7 +316,8 @@ def fit_distributed(spec: E.KernelSpec, x, y, noise: float, device=None, varianc
     factor is NOT W.
 
     comm (optional dict): per-collective bytes and HIP-event times — 'panel_bcast' (one per step),
-    'w_allgather', 'alpha_allgather' (comm_summary)."""
+    'w_allgather', 'alpha_allgather' (comm_summary).  trend: refused (engine.fit(trend=) on one device)."""
+    E.refuse_trend(trend, "fit_distributed", ": use engine.fit(trend=) on one device")
     ws, rank = world()
     if emulate is not None:
         if ws != 1:
@@ -554,7 +559,7 @@ def _allgather_w_columns(A: torch.Tensor, n: int, ws: int, rank: int, dev, comm:
 
 def krige_jobs_sharded(jobs, variance: str = "ozaki", chunk: int = 8192, var_mode: str = "latent",
                        compute_var: bool = True, jitter: float = 0.0, device=None, align: int = 64,
-                       stats: dict | None = None, comm: dict | None = None):
+                       stats: dict | None = None, comm: dict | None = None, trend: str | None = None):
     """A stream of independent kriging jobs (kernel, x, y, noise, xg) — the reference's
     runKrig.py sweep / per-window krig.kriging calls — spread over all ranks: job j is FITTED
     by rank j mod world only (round robin, on a side stream, up to one job per rank ahead),
@@ -572,7 +577,8 @@ def krige_jobs_sharded(jobs, variance: str = "ozaki", chunk: int = 8192, var_mod
     read ahead before the first next(); `stats` counts the fits this rank issues (with their
     host time stamps, engine.note_fit_issued); `comm` collects the factor broadcasts' bytes and
     HIP-event times (comm_summary).  A receiving rank of the ozaki engine keeps only the INT8
-    planes of a job's factor (broadcast_fit planes_only)."""
+    planes of a job's factor (broadcast_fit planes_only).  trend: refused, like engine.krige_jobs."""
+    E.refuse_trend(trend, "krige_jobs_sharded", ": fit and predict each job with engine.fit(trend=)")
     ws, rank = world()
     dev = E._require_device(device)
     if _solo(ws):   # one rank: the single-GPU pipelined form (the next fit under this predict)

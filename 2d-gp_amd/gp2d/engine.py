@@ -286,14 +286,15 @@ class GPFit:
                 _settle(self, host, err)
             finally:
                 _PINNED_STATUS.append(host)
-        return self
+        return _settle_trend(self)
 
     def record_stream(self, stream) -> "GPFit":
         """Mark the fit's device tensors as in use on `stream` — for a fit made on one stream
         and predicted on another: the caching allocator then keeps their memory until the
         work queued on `stream` when they are freed has finished."""
         oz = self.extra.get("ozaki", ())
-        for t in (self.x, self.W, self.alpha, self.y, self.perm, *oz[:2]):
+        tr = self.extra.get("trend") or {}
+        for t in (self.x, self.W, self.alpha, self.y, self.perm, *oz[:2], tr.get("block")):
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 t.record_stream(stream)
         return self
@@ -476,6 +477,118 @@ def ozaki_prepare_guarded(gp: GPFit, diag_add: float, guard: bool = True) -> GPF
     return gp.ready_on(torch.cuda.current_stream(gp.device))
 
 
+# ------------------------------------------------------------------ background flow (trend)
+TRENDS = (None, "constant", "linear")
+
+
+def trend_order(trend) -> int | None:
+    """The library's order of a trend= argument: None (zero-mean), 'constant' → 0, 'linear' → 1."""
+    if trend is None:
+        return None
+    if trend not in N.TREND_ORDERS:
+        raise ValueError(f"trend must be one of {TRENDS}; got {trend!r}")
+    return N.TREND_ORDERS[trend]
+
+
+def refuse_trend(trend, entry: str, hint: str = ""):
+    """ValueError for an entry that has no trend form yet (trend: a trend= argument, or a fit)."""
+    if isinstance(trend, GPFit):
+        trend = trend.extra.get("trend")
+    if trend is not None:
+        raise ValueError(f"{entry} does not support a background flow (trend=){hint}")
+
+
+def _check_trend_fit(kernel: "KernelSpec", variance: str, trend) -> int | None:
+    """A fit's trend= checked before the device is required."""
+    order = trend_order(trend)
+    if order is None:
+        return None
+    if variance == "ozaki":
+        raise ValueError("trend= needs the FP64 engine (variance='f64'): the ozaki variance engine has no trend form")
+    if not kernel.is_vector:
+        raise ValueError("trend= models a background flow (u, v): it needs a vector kernel, not the ARD family")
+    return order
+
+
+def _trend_basis(x, X: torch.Tensor, order: int):
+    """(centre, scale) of the trend's basis coordinates: the mean of the training points' two spatial
+    coordinates and the largest |coordinate − centre| over both axes — on the host for host points
+    (no device round trip), else from the device tensor (one synchronising copy of three numbers)."""
+    if isinstance(x, torch.Tensor):
+        sp = X[:, -2:]
+        c = sp.mean(0)
+        c3 = torch.cat([c, (sp - c).abs().max().reshape(1)]).cpu().numpy()
+        centre, scale = c3[:2], float(c3[2])
+    else:
+        sp = np.asarray(x, dtype=np.float64).reshape(-1, X.shape[1])[:, -2:]
+        centre = sp.mean(0)
+        scale = float(np.abs(sp - centre).max())
+    if not (np.all(np.isfinite(centre)) and np.isfinite(scale)):
+        raise ValueError("trend=: the training points are not finite")
+    if scale == 0.0:   # every point at the centre
+        if order == 1:
+            raise np.linalg.LinAlgError("trend='linear' needs at least three points that are not collinear "
+                                        "(all training points coincide)")
+        scale = 1.0
+    return (float(centre[0]), float(centre[1])), scale
+
+
+def _trend_solve(st: "_Staged", W: torch.Tensor, Y: torch.Tensor, alpha: torch.Tensor, x, order: int, dev,
+                 basis: tuple | None = None) -> dict:
+    """gp2d_trend_fit in place of gp2d_potrs_inv: α′ into alpha and the fit's trend block (β̂, A⁻¹,
+    log|A|, status, [α′ | B0]); returns gp.extra['trend'].  basis: a saved (centre, scale) in place
+    of the training points' own (Krig.load of a checkpoint with its factor)."""
+    L = N.lib()
+    centre, scale = _trend_basis(x, st.X, order) if basis is None else basis
+    desc = N.trend_desc(order, centre, scale)
+    nd = int(L.gp2d_trend_block_doubles(st.n))
+    block = torch.empty(nd + 8, dtype=torch.float64, device=dev)
+    block = block[(-block.data_ptr() % 64) // 8:][:nd]   # 64-byte aligned: a table row is one aligned piece
+    wbytes = int(L.gp2d_trend_workspace(st.n, order))
+    work = _workspace(wbytes, dev)
+    N.check(L.gp2d_trend_fit(_ptr(W), st.n, W.stride(0), _ptr(Y), _ptr(st.X), st.ntr, st.npad, st.X.shape[1],
+                             ctypes.byref(desc), _ptr(alpha), _ptr(block), _ptr(work), wbytes, _stream_handle(dev)),
+            "gp2d_trend_fit")
+    ev = torch.cuda.Event()   # the status word is read after this, whatever stream is current then
+    ev.record(torch.cuda.current_stream(dev))
+    return dict(order=order, name=("constant", "linear")[order], centre=centre, scale=scale, desc=desc, block=block,
+                q=int(L.gp2d_trend_coefficients(order)), event=ev)
+
+
+def _settle_trend(gp: "GPFit") -> "GPFit":
+    """Raise LinAlgError for a trend whose A = H·K_y⁻¹·Hᵀ was singular (the block's status word; read
+    once per fit, after the factor's own status)."""
+    t = gp.extra.get("trend")
+    if t is not None and not t.get("checked"):
+        t["event"].synchronize()
+        st = int(t["block"][N.TREND_STATUS].item())
+        t["checked"] = True
+        if st != 0:
+            raise np.linalg.LinAlgError(
+                f"the trend's normal matrix H·K_y⁻¹·Hᵀ is singular (pivot {st} of {t['q']}): trend='linear' needs "
+                "at least three training points that are not collinear")
+    return gp
+
+
+def trend_coefficients(gp: "GPFit") -> dict:
+    """The estimated background flow of a trend fit, on the host: beta (q,) = β̂ and cov (q, q) = A⁻¹ in
+    the basis coordinates ξ = (x1 − centre[0])/scale, η = (x2 − centre[1])/scale (u = β0 + β2·ξ + β3·η,
+    v = β1 + β4·ξ + β5·η; q = 2 for 'constant'), and the physical reading: mean_flow (u, v) at the
+    centre, and gradient = (∂u/∂x1, ∂u/∂x2, ∂v/∂x1, ∂v/∂x2) of the trend (β/scale; zeros for
+    'constant'), with order, centre and scale."""
+    t = gp.extra.get("trend")
+    if t is None:
+        raise ValueError("trend_coefficients needs a fit made with trend='constant' or 'linear'")
+    gp.check()
+    q = t["q"]
+    head = t["block"][:N.TREND_RHS].cpu().numpy()
+    beta = head[N.TREND_BETA:N.TREND_BETA + q].copy()
+    cov = head[N.TREND_AINV:N.TREND_AINV + N.TREND_AINV_LD ** 2].reshape(N.TREND_AINV_LD, -1)[:q, :q].copy()
+    grad = beta[2:6] / t["scale"] if q == 6 else np.zeros(4)
+    return dict(order=t["name"], centre=np.array(t["centre"]), scale=t["scale"], beta=beta, cov=cov,
+                logdet=float(head[N.TREND_LOGDET]), mean_flow=beta[:2].copy(), gradient=grad)
+
+
 # ------------------------------------------------------------------ the fit's stages
 # (shared by fit, fit_batch, distributed.fit_distributed and krig.Krig._restore)
 @dataclass
@@ -573,7 +686,8 @@ def _make_fit(st: _Staged, noise: float, W: torch.Tensor, alpha: torch.Tensor, Y
 
 
 def _finish_problem(st: _Staged, W: torch.Tensor, y, noise: float, diag_add: float, status: torch.Tensor,
-                    guard: bool | None, variance: str, check: bool, dev, pwork: torch.Tensor | None = None):
+                    guard: bool | None, variance: str, check: bool, dev, pwork: torch.Tensor | None = None,
+                    trend: tuple | None = None):
     """Everything of a fit after W = L⁻¹, queued on the current stream: the guard's statistics
     beside info in `status` (status_block), the status copy of a check=False fit (it reads only
     words written before it, so the host later waits for the factor, not for what follows), α, and
@@ -590,12 +704,18 @@ def _finish_problem(st: _Staged, W: torch.Tensor, y, noise: float, diag_add: flo
     pend = None if check else pending_status(status)
     Y = _pad_obs(y, st.ntr, st.npad, st.kernel.block_dim, dev, st.perm)
     alpha = torch.empty(n, dtype=torch.float64, device=dev)
-    pbytes = int(L.gp2d_potrs_workspace(n))
-    if pwork is None:
-        pwork = _workspace(pbytes, dev)
-    N.check(L.gp2d_potrs_inv(_ptr(W), n, n, _ptr(Y), _ptr(alpha), _ptr(pwork), pbytes, _stream_handle(dev)),
-            "gp2d_potrs_inv")
+    tr = None
+    if trend is not None:   # (order, the caller's points): α′ and the trend block in place of α
+        tr = _trend_solve(st, W, Y, alpha, trend[1], trend[0], dev)
+    else:
+        pbytes = int(L.gp2d_potrs_workspace(n))
+        if pwork is None:
+            pwork = _workspace(pbytes, dev)
+        N.check(L.gp2d_potrs_inv(_ptr(W), n, n, _ptr(Y), _ptr(alpha), _ptr(pwork), pbytes, _stream_handle(dev)),
+                "gp2d_potrs_inv")
     gp = _make_fit(st, noise, W, alpha, Y, dev)
+    if tr is not None:
+        gp.extra["trend"] = tr
     gp.extra["status_dev"] = status   # info + guard statistics on the device (the job stream broadcasts it)
     gp.extra["diag_add"] = float(diag_add)   # noise + jitter on K_y's diagonal (cv_points / cv_groups latent=True)
     del pwork
@@ -622,8 +742,17 @@ def _settle(gp: GPFit, host: torch.Tensor, err) -> GPFit:
 
 
 def fit(kernel: KernelSpec, x, y, noise: float, jitter: float = 0.0, device=None, variance: str = "f64",
-        check: bool = True, jitchol: int = 0, join: bool | None = None, guard: bool | None = None) -> GPFit:
+        check: bool = True, jitchol: int = 0, join: bool | None = None, guard: bool | None = None,
+        trend: str | None = None) -> GPFit:
     """K_y = K(x,x) + (noise+jitter)·I → L = chol(K_y) → W = L⁻¹ → α = Wᵀ W y.
+
+    trend = 'constant' | 'linear' (vector kernels, FP64 engine): a background flow estimated with
+    the fit (universal kriging) — u = β0 + β2·ξ + β3·η, v = β1 + β4·ξ + β5·η in
+    coordinates centred and scaled on the training points.  gp.alpha is then α′ = K_y⁻¹(y − Hᵀβ̂),
+    gp.extra['trend'] holds order, centre, scale and the device block (β̂, its covariance, B0), and
+    predict, predict_field, Predictor and the likelihood route to their trend forms on their own
+    (trend_coefficients reads β̂).  LinAlgError where the basis is not identifiable ('linear' on
+    collinear points or fewer than three distinct ones).
 
     jitchol = k > 0: GPy's jitchol retry (GPy.util.linalg.jitchol, maxtries = k; GPy is not
     installed here, so this follows its published algorithm and is parity-unpinned): if K_y is
@@ -649,7 +778,7 @@ def fit(kernel: KernelSpec, x, y, noise: float, jitter: float = 0.0, device=None
     """
     if jitchol:
         try:
-            gp = fit(kernel, x, y, noise, jitter=jitter, device=device, variance=variance)
+            gp = fit(kernel, x, y, noise, jitter=jitter, device=device, variance=variance, trend=trend)
             gp.extra["jitchol"] = 0.0
             return gp
         except np.linalg.LinAlgError:
@@ -661,7 +790,8 @@ def fit(kernel: KernelSpec, x, y, noise: float, jitter: float = 0.0, device=None
                 if not np.isfinite(jit):
                     break
                 try:
-                    gp = fit(kernel, x, y, noise, jitter=jitter + jit, device=device, variance=variance)
+                    gp = fit(kernel, x, y, noise, jitter=jitter + jit, device=device, variance=variance,
+                             trend=trend)
                     gp.extra["jitchol"] = jit
                     return gp
                 except np.linalg.LinAlgError:
@@ -670,6 +800,7 @@ def fit(kernel: KernelSpec, x, y, noise: float, jitter: float = 0.0, device=None
     if variance not in VARIANCE_ENGINES:
         raise ValueError(f"variance must be one of {VARIANCE_ENGINES}")
     _check_family(kernel, variance)   # before the device is required, like the check above
+    order = _check_trend_fit(kernel, variance, trend)
     dev = _require_device(device)
     st = _stage_problem(kernel, x, variance, dev)
     n, diag_add = st.n, noise + jitter
@@ -679,12 +810,13 @@ def fit(kernel: KernelSpec, x, y, noise: float, jitter: float = 0.0, device=None
     status, info = status_block(dev)   # gp2d_potrf resets info
     _factor_inverse(A, n, dinv, info, dev, join=check if join is None else join)
     del dinv
-    gp, err = _finish_problem(st, A, y, noise, diag_add, status, guard, variance, check, dev)
-    return gp if not check else _settle(gp, status.cpu(), err)
+    gp, err = _finish_problem(st, A, y, noise, diag_add, status, guard, variance, check, dev,
+                              trend=None if order is None else (order, x))
+    return gp if not check else _settle_trend(_settle(gp, status.cpu(), err))
 
 
 def fit_batch(problems, variance: str = "f64", jitter: float = 0.0, device=None, check: bool = True,
-              join: bool | None = None, guard: bool | None = None) -> list:
+              join: bool | None = None, guard: bool | None = None, trend: str | None = None) -> list:
     """Fit several GPs of one size together: `problems` is a sequence of (kernel, x, y, noise)
     whose matrices K_y share the order n (a hyperparameter sweep's settings over one training
     set, or a job stream's next jobs with equal point counts).  Their K_y are factored and
@@ -696,6 +828,7 @@ def fit_batch(problems, variance: str = "f64", jitter: float = 0.0, device=None,
     is in the message); check=False defers it to each GPFit.check().  join, guard as in fit()."""
     if variance not in VARIANCE_ENGINES:
         raise ValueError(f"variance must be one of {VARIANCE_ENGINES}")
+    refuse_trend(trend, "fit_batch", ": fit each problem with engine.fit")
     probs = list(problems)
     if not probs:
         return []
@@ -894,11 +1027,14 @@ class Predictor:
         self.ozaki = "ozaki" in gp.extra
         unit = 128 if (bd == 1 or self.ozaki) else 64
         self.chunk = max(unit, (int(chunk) + unit - 1) // unit * unit)
+        self.trend_order = None
         self.wnmod = 0   # the moduli count the ozaki workspace is sized for (grows on demand)
         if self.ozaki:
             self._ozaki_workspace(gp.extra["ozaki"][2])
         else:
-            self.wbytes = int(N.lib().gp2d_predict_workspace(gp.n, self.chunk, bd))
+            self.trend_order = _trend_of(gp, "order")   # a trend fit's workspace holds q + 1 sets of mean partials
+            self.wbytes = int(N.lib().gp2d_predict_workspace(gp.n, self.chunk, bd)) if self.trend_order is None else \
+                int(N.lib().gp2d_predict_trend_workspace(gp.n, self.chunk, bd, self.trend_order))
             self.work = _workspace(self.wbytes, gp.device)
         self._grid = None   # (the caller's grid tensor, its version, Morton order, the grid in that order)
 
@@ -937,7 +1073,8 @@ class Predictor:
         """True if this workspace serves `gp` as is: same matrix order, engine and block size
         (the FP64 workspace and the chunk rounding depend on the block size)."""
         return (self.gp.n == gp.n and self.ozaki == ("ozaki" in gp.extra)
-                and self.gp.kernel.block_dim == gp.kernel.block_dim)
+                and self.gp.kernel.block_dim == gp.kernel.block_dim
+                and (self.ozaki or self.trend_order == _trend_of(gp, "order")))
 
     def __call__(self, xg, var_mode: str = "latent", compute_var: bool = True, out=None,
                  planes: KstarPlanes | None = None, reuse_grid: bool = False, term: int | None = None):
@@ -988,10 +1125,28 @@ class Predictor:
                 N.check(L.gp2d_predict_ozaki(*fit_args, int(bool(compute_var)), *out_args, _stream_handle(gp.device)),
                         "gp2d_predict_ozaki")
             return mean, (var if compute_var else None)
-        N.check(L.gp2d_predict(*_f64_fit_args(gp, G, desc), _VAR_MODES[var_mode], float(gp.noise),
-                               int(bool(compute_var)), _ptr(mean), _ptr(var), self.chunk, _ptr(self.work),
-                               self.wbytes, _stream_handle(gp.device)), "gp2d_predict")
+        args = (*_f64_fit_args(gp, G, desc), _VAR_MODES[var_mode], float(gp.noise), int(bool(compute_var)), _ptr(mean),
+                _ptr(var), self.chunk, _ptr(self.work), self.wbytes, _stream_handle(gp.device))
+        tr = gp.extra.get("trend")
+        if tr is not None:   # α′ never reaches the plain predict: the trend's terms belong to it
+            if self.trend_order != tr["order"]:
+                raise ValueError("this Predictor's workspace was made for another trend order")
+            N.check(L.gp2d_predict_trend(*args, *_trend_args(tr, term)), "gp2d_predict_trend")
+        else:
+            N.check(L.gp2d_predict(*args), "gp2d_predict")
         return mean, (var if compute_var else None)
+
+
+def _trend_of(gp: GPFit, key: str):
+    """gp.extra['trend'][key], or None for a zero-mean fit."""
+    t = gp.extra.get("trend")
+    return None if t is None else t[key]
+
+
+def _trend_args(tr: dict, term: int | None) -> tuple:
+    """What the trend predicts end with: the descriptor, the block, and whether h* is the basis
+    (not for one term of a sum, whose mean carries no trend)."""
+    return ctypes.byref(tr["desc"]), _ptr(tr["block"]), int(term is None)
 
 
 def _term_kernel(gp: GPFit, term: int | None, var_mode: str = "latent") -> KernelSpec:
@@ -1063,14 +1218,19 @@ def predict_field(gp: GPFit, xg, field: str, compute_var: bool = True, chunk: in
     m = G.shape[0]
     chunk = max(NB, (int(chunk) + NB - 1) // NB * NB)
     chunk = min(chunk, max(NB, (m + NB - 1) // NB * NB))   # no workspace beyond the points there are
-    wbytes = int(L.gp2d_predict_field_workspace(gp.n, chunk))
+    tr = gp.extra.get("trend")
+    wbytes = int(L.gp2d_predict_field_workspace(gp.n, chunk)) if tr is None else \
+        int(L.gp2d_predict_trend_workspace(gp.n, chunk, 1, tr["order"]))
     work = _workspace(wbytes, gp.device)
     mean = torch.empty(m, dtype=torch.float64, device=gp.device)
     var = torch.empty(m, dtype=torch.float64, device=gp.device) if compute_var else None
     desc = _term_kernel(gp, term).desc()
-    N.check(L.gp2d_predict_field(*_f64_fit_args(gp, G, desc), code, int(bool(compute_var)), _ptr(mean),
-                                 None if var is None else _ptr(var), chunk, _ptr(work), wbytes,
-                                 _stream_handle(gp.device)), "gp2d_predict_field")
+    args = (*_f64_fit_args(gp, G, desc), code, int(bool(compute_var)), _ptr(mean), None if var is None else _ptr(var),
+            chunk, _ptr(work), wbytes, _stream_handle(gp.device))
+    if tr is not None:   # the trend's own divergence / vorticity and its variance correction
+        N.check(L.gp2d_predict_field_trend(*args, *_trend_args(tr, term)), "gp2d_predict_field_trend")
+    else:
+        N.check(L.gp2d_predict_field(*args), "gp2d_predict_field")
     return mean, var
 
 
@@ -1099,6 +1259,7 @@ def predict_gradient(gp: GPFit, xg, compute_cov: bool = True, chunk: int = 8192)
     Works for fits of either variance engine, like predict_field.  ValueError for the scalar kind,
     the ARD family, a kernel sum, and a fit without W."""
     _refuse_sum(gp.kernel, "predict_gradient")
+    refuse_trend(gp, "predict_gradient")
     _require_velocity(gp.kernel, "the velocity gradient needs a div-free, curl-free or mixed vector kernel "
                                  "(the scalar kind and the ARD family have none)", gp, "predict_gradient")
     L = N.lib()
@@ -1157,6 +1318,7 @@ def flow_diagnostics(mean, cov=None, names=DIAGNOSTICS) -> dict:
 def _predict_cov_padded(gp: GPFit, xg, diag_add: float):
     """gp2d_predict_cov: (mean (2m,), the padded q × q covariance, m, mp) on the device."""
     _refuse_sum(gp.kernel, "predict_cov")
+    refuse_trend(gp, "predict_cov / sample_posterior")
     _require_velocity(gp.kernel, "the joint covariance needs a div-free, curl-free or mixed vector kernel "
                                  "(the scalar kind and the ARD family are not supported)", gp, "predict_cov")
     L = N.lib()
@@ -1310,7 +1472,7 @@ def note_fit_issued(stats: dict | None):
 def krige_jobs(jobs, variance: str = "ozaki", chunk: int = 8192, var_mode: str = "latent",
                compute_var: bool = True, jitter: float = 0.0, device=None, stats: dict | None = None,
                fits_ahead: int | None = None, batch_fits: int | None = None,
-               batch_ahead: bool | None = None):
+               batch_ahead: bool | None = None, trend: str | None = None):
     """Independent kriging jobs (kernel, x, y, noise, xg), one after another — the reference's
     runKrig.py:1-40 sweep (one GP_laser / krig.kriging fit + grid predict per setting or
     time window) run in one process.  Yields (mean, var) per job, in order, on the current
@@ -1339,6 +1501,7 @@ def krige_jobs(jobs, variance: str = "ozaki", chunk: int = 8192, var_mode: str =
     auto_fit_batch() for the back-to-back form, 1 otherwise.  batch_ahead=True: batch g+1's fit
     on a side stream under batch g's predicts; None (default): auto_batch_ahead() on the first
     job's shape."""
+    refuse_trend(trend, "krige_jobs", ": fit and predict each job with engine.fit(trend=) and engine.predict")
     dev = _require_device(device)
     main = torch.cuda.current_stream(dev)
     first, it = _peek(iter(jobs))
@@ -1652,8 +1815,13 @@ def lml_device(gp: GPFit, eval_gradient: bool = False):
     s = _stream_handle(gp.device)
     bd = gp.kernel.block_dim
     out = torch.empty(1, dtype=torch.float64, device=gp.device)
-    N.check(L.gp2d_lml(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.y), bd * gp.n_train, _ptr(out), s),
-            "gp2d_lml")
+    tr = gp.extra.get("trend")
+    if tr is not None:   # the restricted likelihood: β̂ integrated out under its vague prior
+        N.check(L.gp2d_lml_trend(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.y), bd * gp.n_train,
+                                 ctypes.byref(tr["desc"]), _ptr(tr["block"]), _ptr(out), s), "gp2d_lml_trend")
+    else:
+        N.check(L.gp2d_lml(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.y), bd * gp.n_train, _ptr(out),
+                           s), "gp2d_lml")
     if not eval_gradient:
         return out, None
     desc = gp.kernel.desc()
@@ -1661,8 +1829,13 @@ def lml_device(gp: GPFit, eval_gradient: bool = False):
     wbytes = int(L.gp2d_lml_grad_workspace(gp.n))
     work = _workspace(wbytes, gp.device)
     g = torch.empty(ng, dtype=torch.float64, device=gp.device)
-    N.check(L.gp2d_lml_grad(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
-                            ctypes.byref(desc), _ptr(g), _ptr(work), wbytes, s), "gp2d_lml_grad")
+    if tr is not None:
+        N.check(L.gp2d_lml_grad_trend(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.x), gp.n_train,
+                                      gp.n_pad, ctypes.byref(desc), ctypes.byref(tr["desc"]), _ptr(tr["block"]),
+                                      _ptr(g), _ptr(work), wbytes, s), "gp2d_lml_grad_trend")
+    else:
+        N.check(L.gp2d_lml_grad(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.x), gp.n_train, gp.n_pad,
+                                ctypes.byref(desc), _ptr(g), _ptr(work), wbytes, s), "gp2d_lml_grad")
     return out, g
 
 
@@ -1672,6 +1845,7 @@ CV_MAX_Q = N.CV_MAX_Q   # components of one held-out group (GP2D_CV_MAX_Q)
 
 def _cv_fit(gp: GPFit, entry: str):
     """What both cross-validation entries need of a fit: W, α and the padded observations."""
+    refuse_trend(gp, entry)
     if gp.W is None:
         raise ValueError(f"{entry}: this fit holds no factor W (a receiving rank's planes-only fit); "
                          "cross-validate on the rank that owns the fit")

@@ -144,7 +144,9 @@ class OptResult:
 class Objective:
     """−LML and its gradient in the free coordinates, one HIP fit per evaluation."""
 
-    def __init__(self, kernel, x, y, noise, names, jitter=0.0, device=None):
+    def __init__(self, kernel, x, y, noise, names, jitter=0.0, device=None, trend=None):
+        E.trend_order(trend)   # a trend fit's objective is the restricted likelihood (engine.lml_device)
+        self.trend = trend
         self.kernel, self.noise = kernel, float(noise)
         self.x, self.y = x, y
         self.names = tuple(names)
@@ -165,7 +167,7 @@ class Objective:
         p = self.params(z)
         k, noise = set_params(self.kernel, p)
         try:
-            gp = E.fit(k, self.x, self.y, noise, jitter=self.jitter, device=self.device)
+            gp = E.fit(k, self.x, self.y, noise, jitter=self.jitter, device=self.device, trend=self.trend)
         except np.linalg.LinAlgError:
             return _BAD, np.zeros(len(z))
         val, g = E.log_marginal_likelihood(gp, eval_gradient=True)
@@ -178,13 +180,14 @@ class Objective:
 
 
 def optimize(kernel: E.KernelSpec, x, y, noise: float, fix=(), jitter: float = 0.0, device=None,
-             maxiter: int = 200, start: dict = None, messages: bool = False) -> OptResult:
+             maxiter: int = 200, start: dict = None, messages: bool = False, trend: str | None = None) -> OptResult:
     """Maximise the LML over the free hyperparameters with L-BFGS-B (GPy model.optimize,
     krig.py:450 / laser_io_methods.py:496).  `fix` names parameters to hold (GPy
-    constrain_fixed, GP_plots.py:761-762)."""
+    constrain_fixed, GP_plots.py:761-762).  trend ('constant' | 'linear'): every fit estimates that
+    background flow and the objective is the restricted likelihood; the parameters are the same."""
     from scipy.optimize import minimize
     names = free_names(kernel, fix)
-    obj = Objective(kernel, x, y, noise, names, jitter=jitter, device=device)
+    obj = Objective(kernel, x, y, noise, names, jitter=jitter, device=device, trend=trend)
     p0 = dict(obj.base)
     if start:
         p0.update(start)
@@ -201,7 +204,7 @@ def optimize(kernel: E.KernelSpec, x, y, noise: float, fix=(), jitter: float = 0
 
 def optimize_restarts(kernel: E.KernelSpec, x, y, noise: float, num_restarts: int = 10, fix=(),
                       jitter: float = 0.0, device=None, seed: int = 0, spread: float = 1.0,
-                      maxiter: int = 200, messages: bool = False) -> OptResult:
+                      maxiter: int = 200, messages: bool = False, trend: str | None = None) -> OptResult:
     """GPy model.optimize_restarts (krig.py:450): the first run starts at the current
     hyperparameters, the others at random points within ±spread (free coordinates);
     the best run is returned, all runs are listed in .runs."""
@@ -215,7 +218,7 @@ def optimize_restarts(kernel: E.KernelSpec, x, y, noise: float, num_restarts: in
         if r > 0:
             start = {n: _from_free(n, _to_free(n, base[n]) + rng.uniform(-spread, spread)) for n in names}
         res = optimize(kernel, x, y, noise, fix=fix, jitter=jitter, device=device, maxiter=maxiter, start=start,
-                       messages=messages)
+                       messages=messages, trend=trend)
         runs.append((get_params(res.kernel, res.noise), res.lml))
         if best is None or res.lml > best.lml:
             best = res
@@ -224,7 +227,8 @@ def optimize_restarts(kernel: E.KernelSpec, x, y, noise: float, num_restarts: in
 
 
 def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: float = 0.0, device=None,
-          eval_gradient: bool = False, concurrent: int | None = None, batch: int | None = None):
+          eval_gradient: bool = False, concurrent: int | None = None, batch: int | None = None,
+          trend: str | None = None):
     """LML (and gradient) for each hyperparameter setting (a list of get_params-style dicts,
     missing keys taken from kernel/noise) — BASELINE config E.  Under torch.distributed the
     settings are dealt round-robin over ranks and the results all-reduced (bit-identical to
@@ -240,7 +244,11 @@ def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: flo
     batch = b > 1: the settings are fitted b at a time in one batched factorisation
     (engine.fit_batch: the fit's latency-bound diagonal chain paid once per b settings), then
     each setting's LML (+ gradient) runs on the filled chip; same bits as b = 1.  batch = None
-    (default): auto_batch() — used instead of `concurrent` when it applies."""
+    (default): auto_batch() — used instead of `concurrent` when it applies.
+    trend ('constant' | 'linear'): every setting's fit estimates that background flow and its value
+    is the restricted likelihood; the batched factorisation has no trend form, so the default batch
+    is 1 (an explicit batch > 1 is refused by engine.fit_batch)."""
+    E.trend_order(trend)
     ws, rank = (dist.get_world_size(), dist.get_rank()) if dist.is_available() and dist.is_initialized() else (1, 0)
     base = get_params(kernel, noise if noise is not None else 0.0)
     S = len(settings)
@@ -248,9 +256,11 @@ def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: flo
     vals = np.zeros(S)
     grads = np.zeros((S, P))
     mine = list(range(rank, S, ws))
-    bsz = auto_batch(kernel, x, len(mine), concurrent) if batch is None else max(1, int(batch))
+    bsz = (1 if trend is not None else auto_batch(kernel, x, len(mine), concurrent)) if batch is None \
+        else max(1, int(batch))
     c = auto_concurrent(len(mine), eval_gradient) if concurrent is None else max(1, int(concurrent))
     if bsz > 1:
+        E.refuse_trend(trend, "hyper.sweep(batch > 1)", ": fit_batch has no trend form")
         _sweep_batched(kernel, x, y, settings, base, mine, jitter, device, eval_gradient, bsz, vals, grads)
     elif c == 1:
         for i in mine:
@@ -258,7 +268,7 @@ def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: flo
             p.update(settings[i])
             k, nz = set_params(kernel, p)
             try:
-                gp = E.fit(k, x, y, nz, jitter=jitter, device=device)
+                gp = E.fit(k, x, y, nz, jitter=jitter, device=device, trend=trend)
             except np.linalg.LinAlgError:
                 vals[i] = -np.inf
                 continue
@@ -279,7 +289,7 @@ def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: flo
         prev_sets = E.N.lib().gp2d_factor_sets(c)   # one internal factor stream set per stream
         try:
             _sweep_concurrent(kernel, x, y, settings, base, mine, jitter, dev, eval_gradient, streams, main,
-                              inflight, drain)
+                              inflight, drain, trend)
             drain(0)
         finally:   # any exception (GP2DError, KeyboardInterrupt, ...) restores the process-wide setting
             E.N.lib().gp2d_factor_sets(prev_sets)
@@ -343,7 +353,7 @@ def auto_concurrent(n_settings: int, eval_gradient: bool) -> int:
 
 
 def _sweep_concurrent(kernel, x, y, settings, base, mine, jitter, dev, eval_gradient, streams, main, inflight,
-                      drain):
+                      drain, trend=None):
     c = len(streams)
     for j, i in enumerate(mine):
         p = dict(base)
@@ -355,7 +365,7 @@ def _sweep_concurrent(kernel, x, y, settings, base, mine, jitter, dev, eval_grad
             # joined on the host: the chain never runs with this stream's wait pending
             # beside it (≈ 40 % slower); what overlaps is the previous
             # setting's LML + gradient under this setting's chain
-            gp = E.fit(k, x, y, nz, jitter=jitter, device=dev, check=False, join=True)
+            gp = E.fit(k, x, y, nz, jitter=jitter, device=dev, check=False, join=True, trend=trend)
             out, g = E.lml_device(gp, eval_gradient)
             ev = torch.cuda.Event()
             ev.record(st)

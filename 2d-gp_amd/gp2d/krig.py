@@ -86,12 +86,19 @@ class Krig:
     product, held to the 1e-10 gate by its calibrated accuracy guard (engine.apply_guard: more
     W bits, or FP64 past its range).  The job-stream API (engine.krige_jobs) and bench.py use
     'ozaki'; the drop-in object keeps the reference's arithmetic unless asked.
+    trend: None (zero-mean, the reference's model), 'constant' or 'linear' — a background flow
+    estimated with the fit (engine.fit(trend=); vector kernels, variance='f64').
+    predict*, predict_fields*, log_likelihood (the restricted likelihood) and optimize* then use it;
+    trend_coefficients() reads it; predict_gradient / predict_diagnostics, predict_cov, sample and
+    cross_validate have no trend form yet and raise ValueError.
     """
 
     def __init__(self, kernel="df", l_df: float = 5.0, l_cf: float = 5.0, ratio: float = None,
                  noise: float = 0.0025, jitter: float = 0.0, var_mode: str = "latent", device=None,
-                 chunk: int = 8192, variance: str = "f64", jitchol: int = 0):
+                 chunk: int = 8192, variance: str = "f64", jitchol: int = 0, trend: str | None = None):
         self.spec = self._make_spec(kernel, l_df, l_cf, ratio)
+        E._check_trend_fit(self.spec, variance, trend)   # vector kernels on the FP64 engine
+        self.trend = trend
         self.jitchol = int(jitchol)   # GPy jitchol retries on a non-PD K_y (engine.fit)
         if variance == "ozaki" and not self.spec.is_vector:
             raise ValueError("the ozaki variance engine supports the vector kernels only")
@@ -130,7 +137,7 @@ class Krig:
         if bd == 2 and not isinstance(y, torch.Tensor) and y.ndim == 2 and y.shape[1] == 2:
             y = np.concatenate([y[:, 0], y[:, 1]])
         self.gp = E.fit(self.spec, X, y, self.noise, jitter=self.jitter, device=self.device,
-                        variance=self.variance, jitchol=self.jitchol)
+                        variance=self.variance, jitchol=self.jitchol, trend=self.trend)
         self._pred = E.Predictor(self.gp, self.chunk)
         self._X, self._y = X, y
         return self
@@ -253,6 +260,12 @@ class Krig:
         self._check()
         return E.log_marginal_likelihood(self.gp, eval_gradient=eval_gradient)
 
+    def trend_coefficients(self) -> dict:
+        """The estimated background flow of a trend fit: β̂, its covariance, the mean flow at the
+        centre and the trend's velocity gradient (engine.trend_coefficients)."""
+        self._check()
+        return E.trend_coefficients(self.gp)
+
     def _apply(self, res: "H.OptResult"):
         self.spec, self.noise = res.kernel, float(res.noise)
         self.fit(self._X, self._y)
@@ -262,7 +275,7 @@ class Krig:
         """GPy model.optimize (laser_io_methods.py:496): L-BFGS-B on the LML, refit at the optimum."""
         self._check()
         return self._apply(H.optimize(self.spec, self._X, self._y, self.noise, fix=fix, jitter=self.jitter,
-                                      device=self.device, maxiter=maxiter, messages=messages))
+                                      device=self.device, maxiter=maxiter, messages=messages, trend=self.trend))
 
     def optimize_restarts(self, num_restarts: int = 10, fix=(), seed: int = 0, messages: bool = False,
                           maxiter: int = 200):
@@ -270,7 +283,7 @@ class Krig:
         self._check()
         return self._apply(H.optimize_restarts(self.spec, self._X, self._y, self.noise, num_restarts=num_restarts,
                                                fix=fix, jitter=self.jitter, device=self.device, seed=seed,
-                                               maxiter=maxiter, messages=messages))
+                                               maxiter=maxiter, messages=messages, trend=self.trend))
 
     # ------------------------------------------------------------------ cross-validation
     def cross_validate(self, groups=None, latent: bool = False) -> dict:
@@ -324,6 +337,9 @@ class Krig:
                      sum_weights=np.asarray(s.weights, dtype=np.float64),
                      sum_params=np.array([[t.l_df, t.l_cf, t.ratio, t.var_t, t.l_t] for t in s.terms],
                                          dtype=np.float64))
+        if self.trend is not None:   # the order; with the factor also the basis the block was made with
+            t = self.gp.extra["trend"]
+            d.update(trend=self.trend, trend_centre=np.asarray(t["centre"], dtype=np.float64), trend_scale=t["scale"])
         if with_factor:
             d["W"] = _to_numpy(self.gp.W)
             d["alpha"] = _to_numpy(self.gp.alpha)
@@ -358,20 +374,25 @@ class Krig:
             extra = dict(variance=str(z["variance"]), chunk=int(z["chunk"]))
         if "jitchol" in z.files:
             extra["jitchol"] = int(z["jitchol"])
+        if "trend" in z.files:   # a file without it: the zero-mean model
+            extra["trend"] = str(z["trend"])
         k = cls(spec, noise=float(z["noise"]), jitter=float(z["jitter"]), var_mode=str(z["var_mode"]),
                 device=device, **extra)
         if "W" in z.files:
             used = float(z["jitchol_used"]) if "jitchol_used" in z.files else 0.0
-            k._restore(z["X"], z["y"], z["W"], z["alpha"], z["perm"] if "perm" in z.files else None, used)
+            basis = (tuple(z["trend_centre"].tolist()), float(z["trend_scale"])) if "trend" in z.files else None
+            k._restore(z["X"], z["y"], z["W"], z["alpha"], z["perm"] if "perm" in z.files else None, used, basis)
         elif refit:
             k.fit(z["X"], z["y"])
         return k
 
-    def _restore(self, X, y, W, alpha, perm, jitchol_used: float = 0.0):
+    def _restore(self, X, y, W, alpha, perm, jitchol_used: float = 0.0, trend_basis: tuple | None = None):
         """Rebuild the device fit from a saved factor (no assembly, no factorisation).
         `jitchol_used` is the jitter a jitchol retry added to the saved factor's K_y diagonal:
         the Ozaki residue planes take the a-priori moduli count from the diagonal the factor was
-        built with (noise + jitter + that jitter), exactly as fit() did."""
+        built with (noise + jitter + that jitter), exactly as fit() did.  A trend fit's block is
+        recomputed from the restored W with the saved basis (centre, scale): the same launches on the
+        same inputs as fit()'s, so the same bits."""
         dev = E._require_device(self.device)
         spec = self.spec
         bd, d = spec.block_dim, spec.input_dim
@@ -393,6 +414,10 @@ class Krig:
                          torch.as_tensor(np.ascontiguousarray(alpha), device=dev), Y, dev)
         gp.extra["jitchol"] = float(jitchol_used)
         gp.extra["diag_add"] = float(self.noise + self.jitter)
+        if self.trend is not None:
+            gp.extra["trend"] = E._trend_solve(E._Staged(spec, Xd, ntr, npad, n, pm), gp.W, Y, gp.alpha, X,
+                                               E.trend_order(self.trend), dev, basis=trend_basis)
+            E._settle_trend(gp)
         if self.variance == "ozaki":
             E.ozaki_prepare_guarded(gp, float(self.noise + (self.jitter + jitchol_used)))
         self.gp = gp
@@ -521,7 +546,7 @@ def _prepare(tracks, st, et, lalim, lolim, sample_step, skip, drop_drifters=()):
 
 def kriging(st, et, lalim=(0, 0), lolim=(0, 0), sample_step=5, skip=5, nKernels=1, output="rbfModel",
             pkg="gp2d", kernelType=1, laser=1, tracks: Tracks = None, hyper: dict = None, device=None,
-            drop_drifters=()):
+            drop_drifters=(), trend=None):
     """krig.kriging (krig.py:259-418): build the GP model(s) for a drifter data window.
 
     kernelType 1: scalar ARD RBF on (T, Y, X), one model per component (v, u);
@@ -534,6 +559,8 @@ def kriging(st, et, lalim=(0, 0), lolim=(0, 0), sample_step=5, skip=5, nKernels=
     term's amplitude is its var_t, so its weight defaults to 1.  nKernels = 1 is the one-term model
     and its files, unchanged.  Hyperparameters come from `hyper` (no optimisation here).
     Writes output+'.npz' (the .mat of krig.py:417) and the model files; returns the models.
+    trend ('constant' | 'linear', kernelType 2 / 3 / 4): a background flow estimated with the fit
+    (Krig(trend=)); the first basis coordinate and component are the points' Y and the obs' v.
     """
     if tracks is None:
         raise ValueError("tracks= is required (the reference's Filtered_2016_2_7.pkl is not available)")
@@ -549,7 +576,7 @@ def kriging(st, et, lalim=(0, 0), lolim=(0, 0), sample_step=5, skip=5, nKernels=
         spec = E.KernelSpec(family="ard", variances=tuple([h["variance"]] * nk),
                             lengthscales=tuple([tuple(h["lengthscale"])] * nk))
         for name, obs in (("v", d["vo"]), ("u", d["uo"])):
-            k = Krig(spec, noise=h["noise"], var_mode="gpy", device=device).fit(X, obs[:, 0])
+            k = Krig(spec, noise=h["noise"], var_mode="gpy", device=device, trend=trend).fit(X, obs[:, 0])
             k.save(output + f"_{name}.npz")
             models[name] = k
         obs_all = np.concatenate([d["vo"], d["uo"]], 1)
@@ -571,15 +598,15 @@ def kriging(st, et, lalim=(0, 0), lolim=(0, 0), sample_step=5, skip=5, nKernels=
             terms = tuple(E.KernelSpec(family=fam, kind=kind, l_df=a, l_cf=b, ratio=r, var_t=vt, l_t=lt)
                           for a, b, vt, lt, r in zip(*cols))
             spec = E.KernelSpec(family="vector_sum", terms=terms, weights=tuple(per_term(h["variance"])))
-            k = Krig(spec, noise=h["noise"], var_mode="gpy", device=device).fit(
+            k = Krig(spec, noise=h["noise"], var_mode="gpy", device=device, trend=trend).fit(
                 X if h["temporal"] else X[:, 1:3], obs_all[:, 0])
         elif h["temporal"]:
             spec = E.KernelSpec(family="vector_st", kind=kind, l_df=h["l_df"], l_cf=h["l_cf"], ratio=ratio,
                                 var_t=h["var_t"], l_t=h["l_t"])
-            k = Krig(spec, noise=h["noise"], var_mode="gpy", device=device).fit(X, obs_all[:, 0])
+            k = Krig(spec, noise=h["noise"], var_mode="gpy", device=device, trend=trend).fit(X, obs_all[:, 0])
         else:
             k = Krig(kind, l_df=h["l_df"], l_cf=h["l_cf"], ratio=ratio, noise=h["noise"], var_mode="gpy",
-                     device=device).fit(X[:, 1:3], obs_all[:, 0])
+                     device=device, trend=trend).fit(X[:, 1:3], obs_all[:, 0])
         tag = {2: "_divFree", 3: "_curlFree", 4: "_combined"}[int(kernelType)]
         k.save(output + tag + ".npz")
         models[tag] = k
@@ -823,12 +850,13 @@ def scikit_prior(filename0, varname="v", dt=0, tlim=6, radar="", xlim=(0, 0), yl
     return U, Ustd2
 
 
-def laser(xo, yo, uo, vo, l_df=5, l_cf=5, rate=0.5, noise=0.0025, nsamples=1, dx=0.5, device=None):
+def laser(xo, yo, uo, vo, l_df=5, l_cf=5, rate=0.5, noise=0.0025, nsamples=1, dx=0.5, device=None, trend=None):
     """GP_laser.laser (GP_laser.py:16-142) from projected observations (the pickle /
     pyproj loading of GP_laser.py:26-78 is data plumbing outside the hot path):
     stride-3 split, grid over obs ∪ test ± 5 km, mixed kernel rate·K_df + (1−rate)·K_cf
     + noise·I, posterior mean / variance on the grid and mean at the test points.
-    Returns (x, y, uf, vf, xo, yo, uo, vo, uvar, vvar, xt, yt, ut, vt, uft, vft)."""
+    Returns (x, y, uf, vf, xo, yo, uo, vo, uvar, vvar, xt, yt, ut, vt, uft, vft).
+    trend ('constant' | 'linear'): a background flow estimated with the fit (Krig(trend=))."""
     xo, yo, uo, vo = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (xo, yo, uo, vo))
     if nsamples > 0:
         samples, test = D.split_indices(xo.size, 3)
@@ -837,7 +865,7 @@ def laser(xo, yo, uo, vo, l_df=5, l_cf=5, rate=0.5, noise=0.0025, nsamples=1, dx
     else:
         xt = yt = ut = vt = np.array([0.0])
     x, y, Xs, Ys = D.laser_grid(xo, yo, xt, yt, dx=dx)
-    k = Krig("mixed", l_df=l_df, l_cf=l_cf, ratio=rate, noise=noise, device=device)
+    k = Krig("mixed", l_df=l_df, l_cf=l_cf, ratio=rate, noise=noise, device=device, trend=trend)
     k.fit(np.stack([xo, yo], 1), np.concatenate([uo, vo]))
     uf, vf, uvar, vvar = k.predict_grid(x, y)
     ft, _ = k.predict(np.stack([xt, yt], 1), compute_var=False)

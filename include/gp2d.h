@@ -41,6 +41,8 @@
  * problem stride sA must be even as well.  gp2d_dfact_*'s panel and the packed payload of
  * gp2d_pack_lower / gp2d_ozaki_prepare_packed are GEMM / pair-copy operands too: 16-byte aligned.  Every entry checks its rule on the
  * host before any device work and names the parameter in gp2d_last_error().
+ * The trend entries name W's leading dimension wld: gp2d_trend_fit and gp2d_lml_trend take any
+ * wld >= n (8-byte accesses), the trend predicts and gp2d_lml_grad_trend the even, 16-byte rule.
  */
 #ifndef GP2D_H
 #define GP2D_H
@@ -311,6 +313,79 @@ int gp2d_predict_cov(const double* W, int64_t n, int64_t ldw, const double* alph
                      const double* xg, int64_t m, const gp2d_kernel_t* k, double diag_add,
                      double* mean, double* cov, int64_t ldc,
                      void* work, size_t work_bytes, void* stream);
+
+/* ---- background flow: a constant or linear trend estimated with the fit ------
+ * Universal kriging (a GP with explicit basis functions and a vague prior on their coefficients,
+ * Rasmussen & Williams §2.7) for the vector families (VECTOR2D, VECTOR_ST, VECTOR_SUM; n = 2·ntr_pad).
+ * The reference's models are all zero-mean; these entries replace nothing in it.
+ * Basis coordinates ξ = (x1 − centre[0])/scale, η = (x2 − centre[1])/scale of a point's two SPATIAL
+ * coordinates (its last two: the basis is steady in time for VECTOR_ST), and
+ *   u = β0 + β2·ξ + β3·η,   v = β1 + β4·ξ + β5·η.
+ * order 0 (constant): q = 2 coefficients (β0, β1); order 1 (linear): q = 6 in the order above.
+ * H (q × n): the basis at the observations, zero columns for padded points.  With W = L⁻¹ of K_y:
+ *   G = W·Hᵀ, z = W·y, A = GᵀG, β̂ = A⁻¹Gᵀz, α′ = Wᵀ(z − Gβ̂), B0 = WᵀG = K_y⁻¹Hᵀ.
+ * The trend block (device, gp2d_trend_block_doubles(n) = 48 + 8·n doubles, 64-byte aligned):
+ *   [0, q) β̂ | [8 + 6a + b] A⁻¹[a][b] (the covariance of β̂) | [44] log|A| | [45] status | from 48 the
+ *   right-hand sides, row i = [α′_i, B0[i][0..q), 0…] (8 doubles per row).
+ *   status: 0, or k > 0 when the k-th pivot of A's Cholesky factor is not above 1e-10 of its diagonal
+ *   entry — A is singular to rounding, which a linear trend meets on collinear points or fewer than
+ *   three distinct ones; β̂, A⁻¹ and log|A| are then NaN.  Nothing is regularised.
+ * gp2d_trend_fit: everything above on the device, on `stream`, without a host round trip; writes
+ *   alpha_out = α′ (n) and the block.  In place of gp2d_potrs_inv.  y: the padded observations; dim:
+ *   coordinates per point (2 or 3).  W is read per element through three multi-vector triangular
+ *   products (once for all q + 1 vectors each): any wld >= n, as gp2d_potrs_inv.  Fixed reduction order.
+ * gp2d_predict_trend, gp2d_predict_field_trend: gp2d_predict's and gp2d_predict_field's arguments
+ *   (alpha = α′; wld is their ldw: >= n, even, W 16-byte aligned), then the trend, its block and
+ *   with_basis.  For a target column with cross-covariance k* and basis vector h*
+ *     mean = k*ᵀα′ + h*ᵀβ̂,   var = prior − ‖W k*‖² + rᵀA⁻¹r (+ noise, clipped: var_mode),  r = h* − B0ᵀk*;
+ *   h* is the basis at the target for a velocity component, h_δ = (0,0,1,0,0,1)/scale and
+ *   h_ζ = (0,0,0,−1,1,0)/scale for the derived fields (zero at order 0, where r = −B0ᵀc* remains).
+ *   with_basis = 0 sets h* = 0: the posterior of one term of a sum (the one-term sum as k), which
+ *   carries no trend in its mean but keeps the correction.  The mean pass reads K*ᵀ once for all
+ *   q + 1 right-hand sides; the variance product is gp2d_predict's.  No exact-zero shortcut where a
+ *   field vanishes by kind: the trend's own divergence or vorticity remains.  Workspace:
+ *   gp2d_predict_trend_workspace(n, chunk, bd, order) bytes (bd = 2; 1 for the field entry).
+ *   Deterministic as gp2d_predict: results do not depend on the chunk or the sharding.
+ * gp2d_lml_trend: the restricted likelihood (REML)
+ *     −½‖z − Gβ̂‖² + Σ log W_ii − ½ log|A| − ½(nobs − q) log 2π       (‖z − Gβ̂‖² = yᵀα′).
+ * gp2d_lml_grad_trend: ½ tr((α′α′ᵀ − K_y⁻¹ + B0·A⁻¹·B0ᵀ) ∂K_y/∂θ): gp2d_lml_grad with a rank-q
+ *   update of K_y⁻¹'s stored triangle before the pair loop; its order, count and workspace
+ *   (gp2d_lml_grad_trend_workspace(n) = gp2d_lml_grad_workspace(n)).
+ * Every entry checks on the host, before any launch: order 0 or 1, scale finite and > 0, centre
+ * finite, block not NULL and 64-byte aligned, the workspace size, and the rules of wld.          */
+typedef struct gp2d_trend {
+    int32_t order;       /* 0: constant (q = 2), 1: linear (q = 6)                     */
+    double  centre[2];   /* c: the mean of the training points (spatial coordinates)   */
+    double  scale;       /* s: the largest |coordinate − centre| over both axes        */
+} gp2d_trend_t;
+int    gp2d_trend_coefficients(int order);   /* q: 2 or 6; −2 for another order */
+size_t gp2d_trend_block_doubles(int64_t n);
+size_t gp2d_trend_workspace(int64_t n, int order);
+int gp2d_trend_fit(const double* W, int64_t n, int64_t wld, const double* y,
+                   const double* xtr, int64_t ntr, int64_t ntr_pad, int dim, const gp2d_trend_t* trend,
+                   double* alpha_out, double* block_out, void* work, size_t work_bytes, void* stream);
+size_t gp2d_predict_trend_workspace(int64_t n, int64_t chunk, int bd, int order);
+int gp2d_predict_trend(const double* W, int64_t n, int64_t wld, const double* alpha,
+                       const double* xtr, int64_t ntr, int64_t ntr_pad,
+                       const double* xg, int64_t m, const gp2d_kernel_t* k,
+                       int var_mode, double noise, int compute_var,
+                       double* mean, double* var, int64_t chunk,
+                       void* work, size_t work_bytes, void* stream,
+                       const gp2d_trend_t* trend, const double* block, int with_basis);
+int gp2d_predict_field_trend(const double* W, int64_t n, int64_t wld, const double* alpha,
+                             const double* xtr, int64_t ntr, int64_t ntr_pad,
+                             const double* xg, int64_t m, const gp2d_kernel_t* k, int field,
+                             int compute_var, double* mean, double* var, int64_t chunk,
+                             void* work, size_t work_bytes, void* stream,
+                             const gp2d_trend_t* trend, const double* block, int with_basis);
+int gp2d_lml_trend(const double* W, int64_t n, int64_t wld, const double* alpha, const double* y,
+                   int64_t nobs, const gp2d_trend_t* trend, const double* block, double* lml_dev,
+                   void* stream);
+size_t gp2d_lml_grad_trend_workspace(int64_t n);
+int gp2d_lml_grad_trend(const double* W, int64_t n, int64_t wld, const double* alpha,
+                        const double* xtr, int64_t ntr, int64_t ntr_pad, const gp2d_kernel_t* k,
+                        const gp2d_trend_t* trend, const double* block,
+                        double* grad_dev, void* work, size_t work_bytes, void* stream);
 
 /* ---- predict, FP64-accurate variance on the INT8 matrix cores (Ozaki scheme II) -----
  * Same results contract as gp2d_predict (1e-10 relative parity gate) for the vector2d
