@@ -21,6 +21,7 @@
 #include "factor_host.hpp"
 #include "cv.hpp"
 #include "lml.hpp"
+#include "loo.hpp"
 #include "lml_host.hpp"
 #include "dfact.hpp"
 #include "order.hpp"
@@ -2226,6 +2227,54 @@ int gp2d_kernel_grad(const double* xa, int64_t na, const double* xb, int64_t nb,
   GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_kernel_grad_workspace(na, nb), "kernel_grad: workspace too small");
   return launch_pair_grad(k, xa, na, xb, nb, round_up(nb, PT_TILE), DenseWeights{dL_dK, ld, na, nb},
                           KernelGradWork(na, nb).at(work).partial, 1.0, false, grad_dev, S(stream));
+}
+
+// ------------------------------------------------- leave-one-out density and gradient (loo.hpp)
+size_t gp2d_loo_grad_workspace(int64_t n) { return (n > 0 && n % NB == 0) ? LooGradWork(n).total : 0; }
+
+int gp2d_loo_grad(const double* W, int64_t n, int64_t wld, const double* alpha, const double* y, const double* xtr,
+                  int64_t ntr, int64_t ntr_pad, const gp2d_kernel_t* k, double* value_dev, double* grad_dev,
+                  int* info_dev, void* work, size_t work_bytes, void* stream) {
+  GP2D_CHECK(validate_kernel(k));
+  GP2D_REQUIRE(W && alpha && y && xtr && value_dev && info_dev, "loo_grad: NULL argument");
+  const int bd = gp2d_block_dim(k);
+  GP2D_REQUIRE(ntr_pad > 0 && n == bd * ntr_pad && ntr_pad % PT_TILE == 0,
+               "loo_grad: n must equal block_dim × ntr_pad");
+  GP2D_REQUIRE(n % NB == 0, "loo_grad: n must be a multiple of 128");
+  GP2D_REQUIRE(ntr >= 1 && ntr <= ntr_pad, "loo_grad: ntr must be 1..ntr_pad");
+  GP2D_REQUIRE(ld_even(wld, n), "loo_grad: wld must be >= n and even");
+  GP2D_REQUIRE(aligned16(W), "loo_grad: W must be 16-byte aligned");
+  GP2D_REQUIRE(work != nullptr && work_bytes >= gp2d_loo_grad_workspace(n), "loo_grad: workspace too small");
+  GP2D_REQUIRE(aligned16(work), "loo_grad: workspace must be 16-byte aligned");
+  hipStream_t s = S(stream);
+  const LooGradWork lay(n);
+  const auto w = lay.at(work, n);
+  // P = WᵀW = K_y⁻¹, lower tiles only, as gp2d_lml_grad forms it
+  GemmParams p = gemm_params();
+  p.A = W; p.lda = wld;
+  p.B = W; p.ldb = wld;
+  p.C = w.P; p.ldc = n;
+  p.M = (int)n; p.N = (int)n; p.K = (int)n;
+  p.a_upper = 1; p.c_lower = 1;
+  GP2D_CHECK((launch_gemm<false, EPI_STORE, true>(p, 1, s)));
+  // (α = P·y is the fit's; y enters the objective through it alone)
+  loo_point_kernel<<<1, LOO_POINT_THREADS, 0, s>>>(w.P, n, ntr_pad, ntr, bd, alpha, w.r, w.c11, w.c21, w.c22,
+                                                   value_dev, info_dev);
+  GP2D_CHECK(check_launch("loo_point_kernel"));
+  if (grad_dev == nullptr) return 0;
+  GP2D_CHECK(gp2d_potrs_inv(W, n, wld, w.r, w.s, w.potrs, PotrsWork(n).total, stream));   // s = Wᵀ(W·r)
+  const dim3 grid((unsigned)(ntr_pad / 64), (unsigned)(n / 64));
+  if (bd == 2) loo_scale_kernel<2><<<grid, 256, 0, s>>>(w.P, n, ntr_pad, w.c11, w.c21, w.c22, w.B);
+  else loo_scale_kernel<1><<<grid, 256, 0, s>>>(w.P, n, ntr_pad, w.c11, w.c21, w.c22, w.B);
+  GP2D_CHECK(check_launch("loo_scale_kernel"));
+  GemmParams m = gemm_params();   // M = B·Bᵀ = P·D·P, lower tiles, over P (s and B are formed)
+  m.A = m.B = w.B; m.lda = m.ldb = n;
+  m.C = w.P; m.ldc = n;
+  m.M = m.N = m.K = (int)n;
+  m.c_lower = 1;
+  GP2D_CHECK((launch_gemm<true, EPI_STORE>(m, 1, s)));
+  return launch_pair_grad(k, xtr, ntr, xtr, ntr, ntr_pad, LooWeights{w.P, n, alpha, w.s, ntr_pad}, w.partial, 0.5,
+                          true, grad_dev, s);
 }
 
 // ------------------------------------------------------------------ cross-validation (cv.hpp)

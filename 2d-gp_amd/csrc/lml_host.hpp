@@ -69,4 +69,38 @@ constexpr bool potrs_work_ok(int64_t n) {
 static_assert(potrs_work_ok(128) && potrs_work_ok(256) && potrs_work_ok(8192) && PotrsWork(0).total == 0,
               "potrs workspace: regions out of order, overlapping or misaligned");
 
+// Workspace of gp2d_loo_grad (loo.hpp): P = K_y⁻¹, later M = B·Bᵀ (n × n) | B = P·C (n × n) | r (n) |
+// s = P·r (n) | the Cholesky entries c11, c21, c22 of the D_i (n each: np ≤ n points) | the
+// triangular products' workspace (PotrsWork) | the pair loop's partial sums, sized as LmlGradWork's.
+struct LooGradWork {
+  size_t P = 0, B = 0, r = 0, s = 0, c = 0, potrs = 0, partial = 0, total = 0;
+  constexpr explicit LooGradWork(int64_t n) {
+    const size_t nn = F64 * (size_t)n * (size_t)n, v = F64 * (size_t)n;
+    B = nn;
+    r = B + nn;
+    s = r + v;
+    c = s + v;
+    potrs = c + 3 * v;
+    partial = potrs + PotrsWork(n).total;
+    total = partial + grad_partial_bytes(grad_blocks(n + PT_TILE, n + 1));
+  }
+  struct Ptrs { double *P, *B, *r, *s, *c11, *c21, *c22; void* potrs; double* partial; };
+  Ptrs at(void* w, int64_t n) const {
+    double* cc = work_at(w, c);
+    return {work_at(w, P), work_at(w, B), work_at(w, r), work_at(w, s), cc, cc + n, cc + 2 * n,
+            work_at<char>(w, potrs), work_at(w, partial)};
+  }
+};
+constexpr bool loo_grad_work_ok(int64_t n) {
+  const LooGradWork w(n);
+  const size_t nn = F64 * (size_t)n * (size_t)n, v = F64 * (size_t)n;
+  bool ok = regions_ok({w.P, w.B, w.r, w.s, w.c, w.potrs, w.partial, w.total},
+                       {nn, nn, v, v, 3 * v, PotrsWork(n).total, grad_partial_bytes((n / 64 + 1) * (n / 16 + 1))});
+  for (int bd = 1; bd <= 2; ++bd)   // the fullest launch: ntr = ntr_pad = n / bd
+    ok = ok && w.partial + grad_partial_bytes(grad_blocks(n / bd, n / bd)) <= w.total;
+  return ok && w.potrs % 16 == 0;
+}
+static_assert(loo_grad_work_ok(128) && loo_grad_work_ok(384) && loo_grad_work_ok(8192) && loo_grad_work_ok(32768),
+              "loo_grad workspace: regions out of order, overlapping, misaligned or too few partials");
+
 }  // namespace gp2d

@@ -1980,6 +1980,57 @@ def cv_groups(gp: GPFit, labels, latent: bool = False) -> dict:
     return dict(mean=mean, var=var, resid=resid, lpd=lpd, labels=ids, **_cv_scores(ss[0], ss[1], ss[2], ss[3], nheld))
 
 
+def _loo_call(gp: GPFit, eval_gradient: bool, entry: str):
+    """gp2d_loo_grad on the current stream: (value, grad or None, info) as device tensors.  Refuses
+    what _cv_fit refuses, without the fit's deferred check (no host round trip)."""
+    refuse_trend(gp, entry)
+    if gp.W is None:
+        raise ValueError(f"{entry}: this fit holds no factor W (a receiving rank's planes-only fit); "
+                         "evaluate the objective on the rank that owns the fit")
+    if gp.y is None:
+        raise ValueError(f"{entry}: this fit carries no observations (it was not made by engine.fit)")
+    L, dev = N.lib(), gp.device
+    desc = gp.kernel.desc()
+    out = torch.empty(1, dtype=torch.float64, device=dev)
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    g = torch.empty(int(L.gp2d_lml_grad_count(ctypes.byref(desc))), dtype=torch.float64, device=dev) \
+        if eval_gradient else None
+    wb = int(L.gp2d_loo_grad_workspace(gp.n))
+    work = _workspace(wb, dev)
+    N.check(L.gp2d_loo_grad(_ptr(gp.W), gp.n, gp.W.stride(0), _ptr(gp.alpha), _ptr(gp.y), _ptr(gp.x), gp.n_train,
+                            gp.n_pad, ctypes.byref(desc), _ptr(out), None if g is None else _ptr(g), _ptr(info),
+                            _ptr(work), wb, _stream_handle(dev)), "gp2d_loo_grad")
+    return out, g, info
+
+
+def loo_device(gp: GPFit, eval_gradient: bool = False):
+    """loo_log_likelihood without a host round trip: (value, grad or None) as device tensors, queued
+    on the current stream, as lml_device (hyper.sweep overlaps settings this way).  A fit whose
+    diagonal blocks of K_y⁻¹ are not positive definite gives NaN (loo_log_likelihood raises)."""
+    out, g, _ = _loo_call(gp, eval_gradient, "loo_device")
+    return out, g
+
+
+def loo_log_likelihood(gp: GPFit, eval_gradient: bool = False):
+    """The leave-one-out log predictive density Σ_i log p(y_i | y_−i, X, θ) of a fit — cv_points'
+    mean_lpd × N — and optionally its exact gradient ∂/∂θ in natural units (param_names order), both
+    from the fit without refitting (gp2d_loo_grad; Rasmussen & Williams §5.4.2).
+    The objective that scores hyperparameters by held-out prediction, where log_marginal_likelihood
+    scores them by the evidence; hyper.optimize(objective="loo") maximises it.  Every kernel family
+    of log_marginal_likelihood, both variance engines, ordered and unordered fits; a trend fit is
+    refused.  Raises LinAlgError for a fit whose K_y⁻¹ has a diagonal block that is not positive
+    definite."""
+    gp.check()
+    out, g, info = _loo_call(gp, eval_gradient, "loo_log_likelihood")
+    bad = int(info.item())
+    if bad:
+        raise np.linalg.LinAlgError(f"loo_log_likelihood: the precision block of point {bad - 1} (the fit's order) "
+                                    "is not positive definite (a failed or ill-conditioned fit)")
+    if not eval_gradient:
+        return float(out.item())
+    return float(out.item()), g.cpu().numpy()
+
+
 def _to_host(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
 

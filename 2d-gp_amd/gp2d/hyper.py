@@ -4,7 +4,9 @@ Replaces GPy's model.optimize / optimize_restarts (krig.py:430-468 runRestarts;
 GP_plots.py:673-765; laser_io_methods.py:496-676) and sklearn's internal
 L-BFGS-B restarts (_gpr.py:298-333).  Every objective evaluation is one HIP fit
 (assemble → POTRF → TRTRI → α) plus gp2d_lml / gp2d_lml_grad; only the optimiser
-state (a handful of scalars) lives on the host.
+state (a handful of scalars) lives on the host.  objective="loo" puts the leave-one-out
+log predictive density and its exact gradient (gp2d_loo_grad) in the
+LML's place: the score the reference judges its models by (krig.py:578-646).
 
 Free parameters are optimised in an unconstrained space, as GPy does through its
 constraints (myKernel.py:19-21): length scales, variances and the noise variance
@@ -35,6 +37,20 @@ from . import comm as C
 from . import engine as E
 
 _BAD = 1e25  # objective for a non-positive-definite K_y (rejected by the line search)
+
+OBJECTIVES = ("lml", "loo")   # what optimize maximises; sweep also scores "lgo" (value only)
+
+
+def check_objective(objective, trend=None, allowed=OBJECTIVES, entry="hyper"):
+    """The objective= argument, checked before any device call: 'lml' (the log marginal likelihood)
+    or 'loo' (the leave-one-out log predictive density, engine.loo_log_likelihood), which has no
+    trend form."""
+    if objective not in allowed:
+        raise ValueError(f"{entry}: objective must be one of {allowed}; got {objective!r}")
+    if objective != "lml" and trend is not None:
+        raise ValueError(f"{entry}: objective={objective!r} does not support a background flow "
+                         f"(trend={trend!r}); the leave-out objectives have no trend form")
+    return objective
 
 
 def free_names(kernel: E.KernelSpec, fix=()) -> tuple:
@@ -133,19 +149,27 @@ def _dfree(name, v):
 class OptResult:
     kernel: E.KernelSpec
     noise: float
-    lml: float
+    lml: float               # the log marginal likelihood at the optimum, whatever was maximised
     nit: int = 0
     nfev: int = 0
     success: bool = True
     message: str = ""
-    runs: list = field(default_factory=list)   # per-restart (params dict, lml), GPy optimization_runs
+    runs: list = field(default_factory=list)   # per-restart (params dict, value), GPy optimization_runs
+    objective: str = "lml"   # what was maximised: 'lml' | 'loo'
+    value: float = None      # the maximised objective (= lml for 'lml')
+
+    def __post_init__(self):
+        if self.value is None:
+            self.value = self.lml
 
 
 class Objective:
-    """−LML and its gradient in the free coordinates, one HIP fit per evaluation."""
+    """−objective and its gradient in the free coordinates, one HIP fit per evaluation.  objective:
+    'lml' (engine.log_marginal_likelihood) or 'loo' (engine.loo_log_likelihood)."""
 
-    def __init__(self, kernel, x, y, noise, names, jitter=0.0, device=None, trend=None):
+    def __init__(self, kernel, x, y, noise, names, jitter=0.0, device=None, trend=None, objective="lml"):
         E.trend_order(trend)   # a trend fit's objective is the restricted likelihood (engine.lml_device)
+        self.objective = check_objective(objective, trend, entry="hyper.Objective")
         self.trend = trend
         self.kernel, self.noise = kernel, float(noise)
         self.x, self.y = x, y
@@ -170,7 +194,13 @@ class Objective:
             gp = E.fit(k, self.x, self.y, noise, jitter=self.jitter, device=self.device, trend=self.trend)
         except np.linalg.LinAlgError:
             return _BAD, np.zeros(len(z))
-        val, g = E.log_marginal_likelihood(gp, eval_gradient=True)
+        if self.objective == "loo":
+            try:
+                val, g = E.loo_log_likelihood(gp, eval_gradient=True)
+            except np.linalg.LinAlgError:
+                return _BAD, np.zeros(len(z))
+        else:
+            val, g = E.log_marginal_likelihood(gp, eval_gradient=True)
         del gp
         gd = dict(zip(self.order, g))
         gz = np.array([gd[n] * _dfree(n, p[n]) for n in self.names])
@@ -180,34 +210,55 @@ class Objective:
 
 
 def optimize(kernel: E.KernelSpec, x, y, noise: float, fix=(), jitter: float = 0.0, device=None,
-             maxiter: int = 200, start: dict = None, messages: bool = False, trend: str | None = None) -> OptResult:
+             maxiter: int = 200, start: dict = None, messages: bool = False, trend: str | None = None,
+             objective: str = "lml") -> OptResult:
     """Maximise the LML over the free hyperparameters with L-BFGS-B (GPy model.optimize,
     krig.py:450 / laser_io_methods.py:496).  `fix` names parameters to hold (GPy
     constrain_fixed, GP_plots.py:761-762).  trend ('constant' | 'linear'): every fit estimates that
-    background flow and the objective is the restricted likelihood; the parameters are the same."""
+    background flow and the objective is the restricted likelihood; the parameters are the same.
+    objective='loo' maximises the leave-one-out log predictive density instead (engine.
+    loo_log_likelihood, exact gradient): the result's `value` is that density, its `lml` the LML at
+    the optimum (one more fit); with a trend it is refused."""
     from scipy.optimize import minimize
+    check_objective(objective, trend, entry="hyper.optimize")
     names = free_names(kernel, fix)
-    obj = Objective(kernel, x, y, noise, names, jitter=jitter, device=device, trend=trend)
+    obj = Objective(kernel, x, y, noise, names, jitter=jitter, device=device, trend=trend, objective=objective)
     p0 = dict(obj.base)
     if start:
         p0.update(start)
     z0 = np.array([_to_free(n, p0[n]) for n in names])
     if len(names) == 0:
         val = -obj(z0)[0]
-        return OptResult(kernel, float(noise), val, nfev=1)
+        return OptResult(kernel, float(noise), _lml_at(obj, kernel, float(noise), val), nfev=1,
+                         objective=objective, value=val)
     res = minimize(obj, z0, jac=True, method="L-BFGS-B", options=dict(maxiter=maxiter, disp=bool(messages)))
     p = obj.params(res.x)
     k, nz = set_params(kernel, p)
-    return OptResult(k, nz, float(-res.fun), nit=int(res.nit), nfev=obj.nfev, success=bool(res.success),
-                     message=str(res.message))
+    val = float(-res.fun)
+    return OptResult(k, nz, _lml_at(obj, k, nz, val), nit=int(res.nit), nfev=obj.nfev, success=bool(res.success),
+                     message=str(res.message), objective=objective, value=val)
+
+
+def _lml_at(obj: Objective, kernel, noise, value: float) -> float:
+    """OptResult.lml: the maximised value itself for 'lml'; for another objective the LML of a fit
+    at the optimum (-inf where K_y is not positive definite there)."""
+    if obj.objective == "lml":
+        return value
+    try:
+        gp = E.fit(kernel, obj.x, obj.y, noise, jitter=obj.jitter, device=obj.device)
+    except np.linalg.LinAlgError:
+        return -np.inf
+    return E.log_marginal_likelihood(gp)
 
 
 def optimize_restarts(kernel: E.KernelSpec, x, y, noise: float, num_restarts: int = 10, fix=(),
                       jitter: float = 0.0, device=None, seed: int = 0, spread: float = 1.0,
-                      maxiter: int = 200, messages: bool = False, trend: str | None = None) -> OptResult:
+                      maxiter: int = 200, messages: bool = False, trend: str | None = None,
+                      objective: str = "lml") -> OptResult:
     """GPy model.optimize_restarts (krig.py:450): the first run starts at the current
     hyperparameters, the others at random points within ±spread (free coordinates);
-    the best run is returned, all runs are listed in .runs."""
+    the best run (by `value`, the maximised objective) is returned, all runs are listed in .runs."""
+    check_objective(objective, trend, entry="hyper.optimize_restarts")
     rng = np.random.default_rng(seed)
     names = free_names(kernel, fix)
     base = get_params(kernel, noise)
@@ -218,9 +269,9 @@ def optimize_restarts(kernel: E.KernelSpec, x, y, noise: float, num_restarts: in
         if r > 0:
             start = {n: _from_free(n, _to_free(n, base[n]) + rng.uniform(-spread, spread)) for n in names}
         res = optimize(kernel, x, y, noise, fix=fix, jitter=jitter, device=device, maxiter=maxiter, start=start,
-                       messages=messages, trend=trend)
-        runs.append((get_params(res.kernel, res.noise), res.lml))
-        if best is None or res.lml > best.lml:
+                       messages=messages, trend=trend, objective=objective)
+        runs.append((get_params(res.kernel, res.noise), res.value))
+        if best is None or res.value > best.value:
             best = res
     best.runs = runs
     return best
@@ -228,7 +279,7 @@ def optimize_restarts(kernel: E.KernelSpec, x, y, noise: float, num_restarts: in
 
 def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: float = 0.0, device=None,
           eval_gradient: bool = False, concurrent: int | None = None, batch: int | None = None,
-          trend: str | None = None):
+          trend: str | None = None, objective: str = "lml", labels=None):
     """LML (and gradient) for each hyperparameter setting (a list of get_params-style dicts,
     missing keys taken from kernel/noise) — BASELINE config E.  Under torch.distributed the
     settings are dealt round-robin over ranks and the results all-reduced (bit-identical to
@@ -247,8 +298,24 @@ def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: flo
     (default): auto_batch() — used instead of `concurrent` when it applies.
     trend ('constant' | 'linear'): every setting's fit estimates that background flow and its value
     is the restricted likelihood; the batched factorisation has no trend form, so the default batch
-    is 1 (an explicit batch > 1 is refused by engine.fit_batch)."""
+    is 1 (an explicit batch > 1 is refused by engine.fit_batch).
+    objective='loo': the leave-one-out log predictive density and its gradient (engine.loo_device)
+    in place of the LML, through the same three schedules.  objective='lgo' with labels= (one
+    integer per training point, engine.cv_groups' convention): the summed leave-group-out density
+    of each setting, value only (eval_gradient=True is refused), settings one after another."""
     E.trend_order(trend)
+    check_objective(objective, trend, allowed=OBJECTIVES + ("lgo",), entry="hyper.sweep")
+    if objective == "lgo":
+        if labels is None:
+            raise ValueError("hyper.sweep: objective='lgo' needs labels= (one group id per training point)")
+        if eval_gradient:
+            raise ValueError("hyper.sweep: objective='lgo' has no gradient (eval_gradient=True); the "
+                             "leave-group-out gradient is not built")
+        score = lambda gp, eg: (_lgo_device(gp, labels), None)   # noqa: E731
+    else:
+        if labels is not None:
+            raise ValueError(f"hyper.sweep: labels= belongs to objective='lgo', not {objective!r}")
+        score = E.loo_device if objective == "loo" else E.lml_device
     ws, rank = (dist.get_world_size(), dist.get_rank()) if dist.is_available() and dist.is_initialized() else (1, 0)
     base = get_params(kernel, noise if noise is not None else 0.0)
     S = len(settings)
@@ -259,9 +326,11 @@ def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: flo
     bsz = (1 if trend is not None else auto_batch(kernel, x, len(mine), concurrent)) if batch is None \
         else max(1, int(batch))
     c = auto_concurrent(len(mine), eval_gradient) if concurrent is None else max(1, int(concurrent))
+    if objective == "lgo":   # cv_groups reads its group table on the host: one setting at a time
+        bsz = c = 1
     if bsz > 1:
         E.refuse_trend(trend, "hyper.sweep(batch > 1)", ": fit_batch has no trend form")
-        _sweep_batched(kernel, x, y, settings, base, mine, jitter, device, eval_gradient, bsz, vals, grads)
+        _sweep_batched(kernel, x, y, settings, base, mine, jitter, device, eval_gradient, bsz, vals, grads, score)
     elif c == 1:
         for i in mine:
             p = dict(base)
@@ -272,7 +341,10 @@ def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: flo
             except np.linalg.LinAlgError:
                 vals[i] = -np.inf
                 continue
-            _collect(i, gp, *E.lml_device(gp, eval_gradient), vals, grads)
+            try:
+                _collect(i, gp, *score(gp, eval_gradient), vals, grads)
+            except np.linalg.LinAlgError:   # 'lgo': a group's precision block is not positive definite
+                vals[i] = -np.inf
             del gp
     else:
         dev = E._require_device(device)
@@ -289,10 +361,13 @@ def sweep(kernel: E.KernelSpec, x, y, settings, noise: float = None, jitter: flo
         prev_sets = E.N.lib().gp2d_factor_sets(c)   # one internal factor stream set per stream
         try:
             _sweep_concurrent(kernel, x, y, settings, base, mine, jitter, dev, eval_gradient, streams, main,
-                              inflight, drain, trend)
+                              inflight, drain, trend, score)
             drain(0)
         finally:   # any exception (GP2DError, KeyboardInterrupt, ...) restores the process-wide setting
             E.N.lib().gp2d_factor_sets(prev_sets)
+    if objective == "loo":   # engine.loo_device's NaN: a diagonal block of K_y⁻¹ is not positive definite
+        bad = np.isnan(vals)
+        vals[bad], grads[bad] = -np.inf, 0.0
     if ws > 1:
         vals, grads = allreduce_disjoint(vals, grads, device)
     return vals, (grads if eval_gradient else None)
@@ -326,7 +401,13 @@ def auto_batch(kernel: E.KernelSpec, x, n_settings: int, concurrent=None) -> int
     return max(1, min(BATCH_MAX, n_settings, BATCH_MAX_BYTES // E.fit_problem_bytes(n)))
 
 
-def _sweep_batched(kernel, x, y, settings, base, mine, jitter, device, eval_gradient, bsz, vals, grads):
+def _lgo_device(gp: E.GPFit, labels) -> torch.Tensor:
+    """Σ over the groups of engine.cv_groups' joint log predictive densities, a device scalar."""
+    return E.cv_groups(gp, labels)["lpd"].sum().reshape(1)
+
+
+def _sweep_batched(kernel, x, y, settings, base, mine, jitter, device, eval_gradient, bsz, vals, grads,
+                   score=E.lml_device):
     dev = E._require_device(device)
     for g0 in range(0, len(mine), bsz):
         group = mine[g0:g0 + bsz]
@@ -338,7 +419,7 @@ def _sweep_batched(kernel, x, y, settings, base, mine, jitter, device, eval_grad
             problems.append((k, x, y, nz))
         # joined on the host (the chain runs with no wait pending on this stream, cf. fit(join))
         fits = E.fit_batch(problems, jitter=jitter, device=dev, check=False, join=True)
-        outs = [E.lml_device(gp, eval_gradient) for gp in fits]
+        outs = [score(gp, eval_gradient) for gp in fits]
         for i, gp, (out, g) in zip(group, fits, outs):
             _collect(i, gp, out, g, vals, grads)
         del fits, outs
@@ -353,7 +434,7 @@ def auto_concurrent(n_settings: int, eval_gradient: bool) -> int:
 
 
 def _sweep_concurrent(kernel, x, y, settings, base, mine, jitter, dev, eval_gradient, streams, main, inflight,
-                      drain, trend=None):
+                      drain, trend=None, score=E.lml_device):
     c = len(streams)
     for j, i in enumerate(mine):
         p = dict(base)
@@ -366,7 +447,7 @@ def _sweep_concurrent(kernel, x, y, settings, base, mine, jitter, dev, eval_grad
             # beside it (≈ 40 % slower); what overlaps is the previous
             # setting's LML + gradient under this setting's chain
             gp = E.fit(k, x, y, nz, jitter=jitter, device=dev, check=False, join=True, trend=trend)
-            out, g = E.lml_device(gp, eval_gradient)
+            out, g = score(gp, eval_gradient)
             ev = torch.cuda.Event()
             ev.record(st)
         inflight.append((i, gp, out, g, ev))

@@ -271,19 +271,29 @@ class Krig:
         self.fit(self._X, self._y)
         return res
 
-    def optimize(self, fix=(), messages: bool = False, maxiter: int = 200):
-        """GPy model.optimize (laser_io_methods.py:496): L-BFGS-B on the LML, refit at the optimum."""
+    def loo_log_likelihood(self, eval_gradient: bool = False):
+        """The leave-one-out log predictive density of the current fit (engine.loo_log_likelihood);
+        with eval_gradient also ∂/∂θ in param_array order."""
+        self._check()
+        return E.loo_log_likelihood(self.gp, eval_gradient=eval_gradient)
+
+    def optimize(self, fix=(), messages: bool = False, maxiter: int = 200, objective: str = "lml"):
+        """GPy model.optimize (laser_io_methods.py:496): L-BFGS-B on the LML, refit at the optimum.
+        objective='loo': on the leave-one-out log predictive density instead (hyper.optimize)."""
         self._check()
         return self._apply(H.optimize(self.spec, self._X, self._y, self.noise, fix=fix, jitter=self.jitter,
-                                      device=self.device, maxiter=maxiter, messages=messages, trend=self.trend))
+                                      device=self.device, maxiter=maxiter, messages=messages, trend=self.trend,
+                                      objective=objective))
 
     def optimize_restarts(self, num_restarts: int = 10, fix=(), seed: int = 0, messages: bool = False,
-                          maxiter: int = 200):
-        """GPy model.optimize_restarts (krig.py:450): best of num_restarts L-BFGS-B runs."""
+                          maxiter: int = 200, objective: str = "lml"):
+        """GPy model.optimize_restarts (krig.py:450): best of num_restarts L-BFGS-B runs, ranked by
+        the objective ('lml' | 'loo') they maximise."""
         self._check()
         return self._apply(H.optimize_restarts(self.spec, self._X, self._y, self.noise, num_restarts=num_restarts,
                                                fix=fix, jitter=self.jitter, device=self.device, seed=seed,
-                                               maxiter=maxiter, messages=messages, trend=self.trend))
+                                               maxiter=maxiter, messages=messages, trend=self.trend,
+                                               objective=objective))
 
     # ------------------------------------------------------------------ cross-validation
     def cross_validate(self, groups=None, latent: bool = False) -> dict:
@@ -616,16 +626,17 @@ def kriging(st, et, lalim=(0, 0), lolim=(0, 0), sample_step=5, skip=5, nKernels=
     return models
 
 
-def runRestarts(fname, nres=10, nKernels=2, device=None, seed=0):
+def runRestarts(fname, nres=10, nKernels=2, device=None, seed=0, objective="lml"):
     """krig.runRestarts (krig.py:430-468): load a saved model, optimize_restarts its
-    hyperparameters (nres runs), save it back and print old : new values.  Model files are
+    hyperparameters (nres runs; objective 'lml' | 'loo' as Krig.optimize_restarts), save it back
+    and print old : new values.  Model files are
     .npz (Krig.save) instead of GPy pickles; the restart history is kept in the model file
     (the reference's fname_dict.pkl workaround, krig.py:439-457, is not needed)."""
     t0 = time.time()
     filename = fname if fname.endswith(".npz") else fname + ".npz"
     model = Krig.load(filename, device=device)
     hyp_old = model.param_array.copy()
-    res = model.optimize_restarts(num_restarts=nres, seed=seed)
+    res = model.optimize_restarts(num_restarts=nres, seed=seed, objective=objective)
     hyp = model.param_array
     model.save(filename)
     print("Optimized Hyperparameters =================================================")

@@ -43,6 +43,7 @@
  * host before any device work and names the parameter in gp2d_last_error().
  * The trend entries name W's leading dimension wld: gp2d_trend_fit and gp2d_lml_trend take any
  * wld >= n (8-byte accesses), the trend predicts and gp2d_lml_grad_trend the even, 16-byte rule.
+ * gp2d_loo_grad names it wld too and takes the even, 16-byte rule.
  */
 #ifndef GP2D_H
 #define GP2D_H
@@ -596,6 +597,28 @@ int gp2d_cv_groups(const double* W, int64_t n, int64_t ldw, const double* alpha,
                    int64_t ntr, int64_t npad, int bd, const int64_t* gstart, const int64_t* gidx,
                    int ngroups, const int64_t* out_order, double* mean, double* var,
                    double* lpd_group, int* info_group, void* work, size_t work_bytes, void* stream);
+
+/* ---- the leave-one-out objective and its gradient (added within ABI 11) ----
+ * gp2d_loo_grad: value_dev (1 device double) = L_LOO = Σ_i lpd_i, the summed log predictive
+ *   density of every training point's observation (its u and v together) given all the others —
+ *   summary[0] of gp2d_cv_points — and grad_dev (device, gp2d_lml_grad_count(k) doubles, in
+ *   gp2d_lml_grad's order and natural units, noise last) its exact gradient
+ *     ∂L_LOO/∂θ = ½ tr((α sᵀ + s αᵀ − P·D·P) ∂K_y/∂θ),  P = K_y⁻¹ = WᵀW,  r_i = P_ii⁻¹·α_i,
+ *     s = P·r,  D = blockdiag(r_i r_iᵀ + P_ii⁻¹)
+ *   (Rasmussen & Williams §5.4.2; bd = 1: eq. 5.13).  Reads only (W, alpha, the points and k): every
+ *   kernel family of gp2d_lml_grad, sums included, and both variance engines.  y is the padded
+ *   observation vector of the fit (alpha = P·y carries it; it must not be NULL).  grad_dev = NULL:
+ *   the value only (the product WᵀW and the point pass).  info_dev (1 device int): 0, or 1 + the
+ *   first point (the fit's order) whose P_ii or D_i is not positive definite — a failed fit;
+ *   value_dev is then NaN and the gradient void.  W's leading dimension is wld: wld >= n, even, W
+ *   16-byte aligned (gp2d_lml_grad's rule).  n = block_dim × ntr_pad, a multiple of 128.  Workspace
+ *   gp2d_loo_grad_workspace(n) bytes (≈ 2·n² doubles; 0 for a bad n), 16-byte aligned.  No atomics,
+ *   fixed summation order: repeat calls give the same bits.                                      */
+size_t gp2d_loo_grad_workspace(int64_t n);
+int gp2d_loo_grad(const double* W, int64_t n, int64_t wld, const double* alpha, const double* y,
+                  const double* xtr, int64_t ntr, int64_t ntr_pad, const gp2d_kernel_t* k,
+                  double* value_dev, double* grad_dev, int* info_dev,
+                  void* work, size_t work_bytes, void* stream);
 
 /* ---- dense helpers (the GP_scripts functional API on explicit matrices) ------------
  * gp2d_gemm: C = alpha·A·op(B) + beta·C on the FP64 MFMA GEMM core; op(B) = B (transb = 0,
