@@ -14,6 +14,7 @@
 #include "trend.hpp"
 #include "fields.hpp"
 #include "grad.hpp"
+#include "advect.hpp"
 #include "postcov.hpp"
 #include "predict_host.hpp"
 #include "ozaki.hpp"
@@ -1501,6 +1502,65 @@ int gp2d_predict_grad(const double* W, int64_t n, int64_t ldw, const double* alp
   };
   const auto [C, pm, G] = PredictGradWork(n, chunk).at(work);
   return predict_chunks(v, W, n, ldw, alpha, ntr, xg, point_dim(k), m, compute_cov, mean, cov, chunk, C, pm, G, s);
+}
+
+// ------------------------------------------------- ADVECT (trajectories and the flow map's gradient)
+int64_t gp2d_advect_records(int nsteps, int save_every) {
+  GP2D_REQUIRE(nsteps >= 0, "advect_records: nsteps must be >= 0");
+  GP2D_REQUIRE(save_every >= 1, "advect_records: save_every must be >= 1");
+  return 1 + ((int64_t)nsteps + save_every - 1) / save_every;
+}
+
+int gp2d_advect(const double* alpha, int64_t n, const double* xtr, int64_t ntr, int64_t ntr_pad,
+                const gp2d_kernel_t* k, const gp2d_trend_t* trend, const double* block, const double* x0, int64_t m,
+                double t0, double dt, int nsteps, int save_every, double vel_scale, double* path, double* tangent,
+                void* stream) {
+  if (validate_kernel(k) != 0) {
+    set_error("advect: k is invalid: " + g_err);
+    return -2;
+  }
+  GP2D_REQUIRE(field_kernel_ok(k),
+               "advect: k must be a div-free, curl-free or mixed vector kernel (KIND_SCALAR and the ARD family "
+               "have no velocity gradient)");
+  GP2D_REQUIRE(ntr_pad > 0 && ntr_pad % PT_TILE == 0, "advect: ntr_pad must be a positive multiple of 64");
+  GP2D_REQUIRE(n == 2 * ntr_pad, "advect: n must equal 2 × ntr_pad");
+  GP2D_REQUIRE(ntr > 0 && ntr <= ntr_pad, "advect: ntr must be in 1..ntr_pad");
+  GP2D_REQUIRE(nsteps >= 0, "advect: nsteps must be >= 0");
+  GP2D_REQUIRE(save_every >= 1, "advect: save_every must be >= 1");
+  GP2D_REQUIRE(nsteps == 0 || (std::isfinite(dt) && dt != 0.0), "advect: dt must be finite and non-zero");
+  GP2D_REQUIRE(std::isfinite(t0), "advect: t0 must be finite");
+  GP2D_REQUIRE(std::isfinite(vel_scale), "advect: vel_scale must be finite");
+  GP2D_REQUIRE((trend == nullptr) == (block == nullptr),
+               "advect: trend and block must be both NULL (a zero-mean fit) or both set");
+  if (trend != nullptr) GP2D_CHECK(validate_trend(trend, block, "advect"));
+  GP2D_REQUIRE(m >= 0 && m < (int64_t)1 << 36, "advect: m out of range");
+  if (m == 0) return 0;
+  GP2D_REQUIRE(alpha != nullptr, "advect: alpha is NULL");
+  GP2D_REQUIRE(xtr != nullptr, "advect: xtr is NULL");
+  GP2D_REQUIRE(x0 != nullptr, "advect: x0 is NULL");
+  GP2D_REQUIRE(path != nullptr, "advect: path is NULL");
+  hipStream_t s = S(stream);
+  const AdvectKernel ak = make_advect_kernel(k);
+  AdvectTrend at{0, TrendBasis{0.0, 0.0, 1.0}, nullptr};
+  if (trend != nullptr) at = AdvectTrend{trend_q(trend->order), trend_basis_of(trend), block};
+  const bool st = point_dim(k) == 3;
+  const unsigned grid = (unsigned)((m + ADV_TILE - 1) / ADV_TILE);
+  advect_init_kernel<<<(unsigned)((m + 255) / 256), 256, 0, s>>>(x0, m, path, tangent);
+  GP2D_CHECK(check_launch("advect_init_kernel"));
+  // one launch per saved segment: record r → record r + 1, never more than save_every steps
+  int64_t r = 0;
+  for (int n0 = 0; n0 < nsteps; n0 += save_every, ++r) {
+    const int nst = std::min(save_every, nsteps - n0);
+    const double* xin = path + r * m * 2;
+    double* xout = path + (r + 1) * m * 2;
+    const double* fin = tangent ? tangent + r * m * 4 : nullptr;
+    double* fout = tangent ? tangent + (r + 1) * m * 4 : nullptr;
+    GP2D_CHECK(st ? launch_advect<true>(tangent != nullptr, grid, s, alpha, xtr, ntr, ntr_pad, ak, at, xin, fin, xout,
+                                        fout, m, t0, dt, n0, nst, vel_scale)
+                  : launch_advect<false>(tangent != nullptr, grid, s, alpha, xtr, ntr, ntr_pad, ak, at, xin, fin,
+                                         xout, fout, m, t0, dt, n0, nst, vel_scale));
+  }
+  return 0;
 }
 
 // ------------------------------------------------- PREDICT (joint posterior covariance)

@@ -1315,6 +1315,68 @@ def flow_diagnostics(mean, cov=None, names=DIAGNOSTICS) -> dict:
     return out
 
 
+def advect_records(nsteps: int, save_every: int) -> int:
+    """The records an advect call returns: 1 + ⌈nsteps / save_every⌉ (gp2d_advect_records)."""
+    r = int(N.lib().gp2d_advect_records(int(nsteps), int(save_every)))
+    if r < 0:
+        raise ValueError(N.lib().gp2d_last_error().decode(errors="replace"))
+    return r
+
+
+def advect(gp: GPFit, x0, t0: float = 0.0, dt: float = None, nsteps: int = None, save_every: int | None = None,
+           vel_scale: float = 1.0, tangent: bool = False):
+    """Advect particles through the fitted mean flow: classical RK4 of dx/dt = s·μ(x, t) from the
+    start positions x0 (m, 2) at time t0, nsteps steps of size dt (negative: backward in time), with
+    s = vel_scale the factor from velocity units to position units per time unit (3.6: m/s → km/h).
+    Returns device tensors (times (R,), path (R, m, 2), tangent (R, m, 2, 2) | None): record 0 is the
+    start, record r the state after step min(r·save_every, nsteps); save_every=None records the end
+    only.  tangent=True integrates the flow map's gradient F[a][b] = ∂x_a(t)/∂x_b(t0) along
+    (dF/dt = s·∇μ·F, F(t0) = I; ftle() takes it); without it the gradient terms are not evaluated and
+    the path is the same to the bit.
+
+    Points (x1, x2) and components (f1, f2) = the first and second half of the observations:
+    dx1/dt = s·f1, dx2/dt = s·f2, so points (Y, X) with observations [v; u] are consistent as they
+    stand.  A 'vector_st' fit is evaluated at the stage's time t; the spatial families are steady.
+    One fused kernel per record reads only gp.alpha, gp.x and the trend's β̂ (gp2d_advect, DESIGN.md
+    §3.13): kernel sums and trend fits are covered, and a fit of either variance engine serves — α
+    and x share the fit's order and the start points are the caller's —, also one without W.  A
+    particle's results do not depend on the other particles of the call: x0 may be sharded freely.
+    ValueError for the scalar kind and the ARD family."""
+    _require_velocity(gp.kernel, "advection needs a div-free, curl-free or mixed vector kernel "
+                                 "(the scalar kind and the ARD family have no velocity field to follow)")
+    if dt is None or nsteps is None:
+        raise ValueError("advect needs dt and nsteps")
+    nsteps = int(nsteps)
+    save_every = max(nsteps, 1) if save_every is None else int(save_every)
+    R = advect_records(nsteps, save_every)
+    L = N.lib()
+    X0 = _as_points(x0, 2, gp.device)
+    m = X0.shape[0]
+    path = torch.empty((R, m, 2), dtype=torch.float64, device=gp.device)
+    tan = torch.empty((R, m, 2, 2), dtype=torch.float64, device=gp.device) if tangent else None
+    desc = gp.kernel.desc()
+    tr = gp.extra.get("trend")
+    targs = (None, None) if tr is None else (ctypes.byref(tr["desc"]), _ptr(tr["block"]))
+    N.check(L.gp2d_advect(_ptr(gp.alpha), gp.n, _ptr(gp.x), gp.n_train, gp.n_pad, ctypes.byref(desc), *targs,
+                          _ptr(X0), m, float(t0), float(dt), nsteps, save_every, float(vel_scale), _ptr(path),
+                          None if tan is None else _ptr(tan), _stream_handle(gp.device)), "gp2d_advect")
+    steps = torch.clamp(torch.arange(R, dtype=torch.float64, device=gp.device) * save_every, max=float(nsteps))
+    return float(t0) + steps * float(dt), path, tan
+
+
+def ftle(tangent, duration: float):
+    """The finite-time Lyapunov exponent ln λ_max(FᵀF) / (2·|duration|) of flow-map gradients F
+    (..., 2, 2) — advect's tangent at a record, `duration` the time integrated to it.  Ridges of the
+    field over a grid of seeds are the transport barriers (repelling for dt > 0, attracting for
+    dt < 0).  The closed form for a symmetric 2 × 2 matrix; pure torch, on any device, broadcasting
+    over the leading dimensions."""
+    F = torch.as_tensor(tangent)
+    a, b, c, d = F[..., 0, 0], F[..., 0, 1], F[..., 1, 0], F[..., 1, 1]
+    p, q, r = a * a + c * c, a * b + c * d, b * b + d * d   # FᵀF = [[p, q], [q, r]]
+    lam = 0.5 * (p + r) + torch.sqrt(0.25 * (p - r) ** 2 + q * q)
+    return torch.log(lam) / (2.0 * abs(float(duration)))
+
+
 def _predict_cov_padded(gp: GPFit, xg, diag_add: float):
     """gp2d_predict_cov: (mean (2m,), the padded q × q covariance, m, mp) on the device."""
     _refuse_sum(gp.kernel, "predict_cov")

@@ -226,6 +226,32 @@ class Krig:
         shp = [np.size(y), -1]
         return {name: (mu.reshape(shp), var.reshape(shp)) for name, (mu, var) in self.predict_diagnostics(pts).items()}
 
+    # ------------------------------------------------------------------ trajectories, FTLE
+    def advect(self, X0, t0: float = 0.0, dt: float = None, nsteps: int = None, save_every: int | None = None,
+               vel_scale: float = 1.0, tangent: bool = False):
+        """Trajectories of particles released at the points X0 (M, 2) at time t0 in the fitted mean
+        flow: (times (R,), path (R, M, 2), tangent (R, M, 2, 2) | None) numpy arrays — RK4 with
+        nsteps steps of dt (negative: backward), a record every save_every steps and at the end
+        (None: start and end only), vel_scale from velocity units to position units per time unit;
+        tangent=True adds the flow map's gradient ∂x(t)/∂x(t0) (engine.advect).  Points and
+        components pair as in the fit: (x, y) with obs [u; v], or (Y, X) with obs [v; u]."""
+        self._check()
+        t, path, tan = E.advect(self.gp, X0, t0=t0, dt=dt, nsteps=nsteps, save_every=save_every,
+                                vel_scale=vel_scale, tangent=tangent)
+        return _to_numpy(t), _to_numpy(path), (None if tan is None else _to_numpy(tan))
+
+    def ftle_grid(self, x, y, t0: float, duration: float, nsteps: int, vel_scale: float = 1.0):
+        """The finite-time Lyapunov exponent field of the fitted flow over `duration` (negative:
+        backward, attracting structures) from t0, seeded on the grid meshgrid(x, y) of predict_grid
+        (points (x, y), components (u, v)) and integrated in nsteps RK4 steps: [y.size, x.size]
+        (engine.ftle of engine.advect's tangent at the final record)."""
+        self._check()
+        X, Y = np.meshgrid(x, y)
+        pts = np.stack([X.reshape(-1), Y.reshape(-1)], 1)
+        _, _, tan = E.advect(self.gp, pts, t0=t0, dt=float(duration) / int(nsteps), nsteps=nsteps,
+                             vel_scale=vel_scale, tangent=True)
+        return _to_numpy(E.ftle(tan[-1], duration)).reshape([np.size(y), -1])
+
     # ------------------------------------------------------------------ joint covariance, samples
     def predict_cov(self, Xg):
         """(mean (2M, 1), cov (2M, 2M)) numpy arrays: the posterior mean and the full latent

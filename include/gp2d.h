@@ -101,9 +101,9 @@ typedef struct gp2d_kernel {
  * one-term sum (w_t, term t) as its kernel is the posterior of term t's contribution alone.
  * Accepted by gp2d_block_dim (2), gp2d_kernel_diag (Σ w_t·diag_t), gp2d_assemble (every `symmetric`
  * mode), gp2d_assemble_cols, gp2d_predict, gp2d_field_prior_var (Σ w_t·var_t), gp2d_predict_field
- * (every term non-scalar; exact zeros only where the field vanishes in every term) and the four
- * gradient entries.  Gradient order: per term t (weight_t, then the term's own entries in its
- * family's order without noise: l_df, l_cf, ratio[, var_t, l_t]), then noise (gp2d_lml_grad only);
+ * (every term non-scalar; exact zeros only where the field vanishes in every term), gp2d_advect
+ * (every term non-scalar) and the four gradient entries.  Gradient order: per term t (weight_t,
+ * then the term's own entries in its family's order without noise: l_df, l_cf, ratio[, var_t, l_t]), then noise (gp2d_lml_grad only);
  * ∂/∂w_t = Σ weights ⊙ K_t.  gp2d_predict_grad, gp2d_grad_prior_cov, gp2d_predict_cov and every
  * ozaki entry that takes a kernel refuse a sum on the host (the int8 engine has no K* instantiation,
  * scale bound or fitted error model for sums).                                                    */
@@ -619,6 +619,47 @@ int gp2d_loo_grad(const double* W, int64_t n, int64_t wld, const double* alpha, 
                   const double* xtr, int64_t ntr, int64_t ntr_pad, const gp2d_kernel_t* k,
                   double* value_dev, double* grad_dev, int* info_dev,
                   void* work, size_t work_bytes, void* stream);
+
+/* ---- advection through the fitted flow: trajectories and the flow map's gradient (DESIGN.md §3.13;
+ * added within ABI 11) ----
+ * Classical RK4 of the augmented system
+ *     dx/dt = s·μ(x, t),   dF/dt = s·∇μ(x, t)·F,   F(t0) = I
+ * for m particles: μ(x, t) = K(x, X)·α (+ h(x)ᵀβ̂ for a trend fit) is the posterior mean velocity of
+ * the fit, ∇μ its 2 × 2 gradient in gp2d_predict_grad's component order c = 2a + b (a linear trend
+ * adds (β2, β3; β4, β5)/scale), s = vel_scale the factor from velocity units to position units per
+ * time unit (3.6: m/s → km/h).  Points (x1, x2) and components (f1, f2) = the first and second half of
+ * the observation vector: dx1/dt = s·f1, dx2/dt = s·f2 — the pairing of every other entry, so a
+ * caller whose points are (Y, X) with observations [v; u] is consistent as it stands.  VECTOR_ST:
+ * training rows are (t, x1, x2) and the stage times t, t + dt/2, t + dt/2, t + dt; step n starts at
+ * t0 + n·dt.  The purely spatial families ignore t (a steady flow).  Replaces nothing in the
+ * reference, which only reads tracks (laser_io_methods.py); a caller of gp2d_predict would loop it
+ * four times per step.
+ * Reads only alpha (n = 2·ntr_pad doubles: α_u[i], α_v[ntr_pad + i]; α′ of a trend fit), the
+ * training points xtr (ntr rows, no padded rows are read) and, for a trend fit, the descriptor and
+ * the block's β̂ — no W: a fit of either variance engine serves, also one that kept no factor.  trend
+ * and block: both NULL for a zero-mean fit, else as for gp2d_predict_trend.  No workspace.
+ * Kernels: VECTOR2D, VECTOR_ST and VECTOR_SUM of kinds DIVFREE, CURLFREE or MIXED (a sum: every
+ * term); KIND_SCALAR and the ARD family are refused, as in gp2d_predict_grad.
+ * gp2d_advect_records: R = 1 + ⌈nsteps / save_every⌉, the records a call writes; < 0 on bad input.
+ * gp2d_advect: x0 (m × 2) the start positions at t0; path (R·m·2 doubles, [r][j][2]): record 0 is
+ *   x0, record r the positions after step min(r·save_every, nsteps).  tangent: NULL, or R·m·4
+ *   doubles [r][j][2a + b] = ∂x_a(t_r)/∂x_b(t0), record 0 the identity; with NULL the gradient terms
+ *   are not evaluated and the path keeps its bits.  dt < 0 integrates backward in time.  nsteps = 0
+ *   writes record 0 only; m = 0 returns 0 without a launch.  One launch per record — no kernel runs
+ *   more than save_every steps — which reads record r and writes record r + 1; the state passes
+ *   through memory in FP64, so the results do not depend on save_every.  A particle's results do not
+ *   depend on m, on its index or on the other particles of the call (no atomics, fixed summation
+ *   order): a caller may shard x0 freely.  A non-finite start position gives NaN in every record of
+ *   that particle's path and in its tangent records after the first, and touches nothing else.
+ *   Checked on the host before any device work, each naming its parameter: k's family and kind,
+ *   n == 2·ntr_pad, 0 < ntr ≤ ntr_pad, nsteps ≥ 0, save_every ≥ 1, dt finite and non-zero when
+ *   nsteps > 0, t0 and vel_scale finite, trend and block both NULL or both set and the trend entries'
+ *   rules (order, scale, centre, 64-byte block alignment), the pointers not NULL when m > 0.      */
+int64_t gp2d_advect_records(int nsteps, int save_every);
+int gp2d_advect(const double* alpha, int64_t n, const double* xtr, int64_t ntr, int64_t ntr_pad,
+                const gp2d_kernel_t* k, const gp2d_trend_t* trend, const double* block,
+                const double* x0, int64_t m, double t0, double dt, int nsteps, int save_every, double vel_scale,
+                double* path, double* tangent, void* stream);
 
 /* ---- dense helpers (the GP_scripts functional API on explicit matrices) ------------
  * gp2d_gemm: C = alpha·A·op(B) + beta·C on the FP64 MFMA GEMM core; op(B) = B (transb = 0,
