@@ -1900,31 +1900,43 @@ static int predict_ozaki_impl(const int8_t* wres, const double* rowscale, int nm
       // grid.z: no launch gap and no tail between the moduli, −3 % per chunk at n = 2048,
       // profiles/r04_zbatch.txt); large n: one launch per modulus (the same within 0.2 %).  Three
       // products: always every modulus in one launch per product — three shorter launches per
-      // modulus would each end in a tail of their own (measured)
+      // modulus would each end in a tail of their own (measured).  With the K* planes
+      // in the workspace the three products are independent: P3 goes into the planes' unread block
+      // and the CRT pass adds the residues; with the caller's planes P2 and P3 add P1 in their epilogue
       const bool three = ozaki_three(n);
-      const OzakiProducts prods(n, cp, three);
+      const OzakiProducts prods(n, cp, three, !pre);
       const int zper = (three || n <= kIgemmZBatchMaxN) ? nm : 1;
       for (int l0 = 0; l0 < nm; l0 += zper) {
         const int nz = std::min(zper, nm - l0);
-        IgemmZ zb{(int64_t)n * n, (int64_t)bplane, (int64_t)n * ncols, {}};
-        for (int u = 0; u < nz; ++u) zb.m[u] = oc.m[l0 + u];
         // 256 output columns per workgroup, one workgroup per CU (the 128-wide shape with two
         // workgroups per CU measured −5 %: tools/microbench/igemm_bench.hip)
         constexpr int tbn = 256, nst = I_NSTAGE;
         const int8_t* Al = wres + (size_t)l0 * n * n;
         const int8_t* Bl = B + (size_t)l0 * bplane;
-        uint8_t* Cl = cres + (size_t)l0 * n * ncols;
         for (int q = 0; q < prods.count; ++q) {
+          // the output: V's plane in cres, or (P3 where the CRT pass sums) its place in the K* planes
+          const bool in_b = prods.sum_in_crt && q == 2;
+          uint8_t* Cl = in_b ? reinterpret_cast<uint8_t*>(bres) + (size_t)l0 * bplane + prods.p3_off
+                             : cres + (size_t)l0 * n * ncols;
+          IgemmZ zb{(int64_t)n * n, (int64_t)bplane, in_b ? (int64_t)bplane : (int64_t)n * ncols, {}};
+          for (int u = 0; u < nz; ++u) zb.m[u] = oc.m[l0 + u];
           const dim3 ggrid(prods.gx[q], prods.gy[q], (unsigned)nz);
-          igemm_nt_mod_kernel<tbn, nst><<<ggrid, 2 * tbn, 0, s>>>(Al, Bl, Cl, n, kslabs, oc.m[l0], prods.prod[q],
-                                                                  use_skip ? slist : nullptr,
+          igemm_nt_mod_kernel<tbn, nst><<<ggrid, 2 * tbn, 0, s>>>(Al, Bl, Cl, in_b ? n / 2 : n, kslabs, oc.m[l0],
+                                                                  prods.prod[q], use_skip ? slist : nullptr,
                                                                   use_skip ? scnt : nullptr, zb);
           GP2D_CHECK(check_launch("igemm_nt_mod_kernel"));
         }
       }
       timed.stop();
-      const dim3 cgrid((unsigned)((ncols + OZ_CRT_BCOLS - 1) / OZ_CRT_BCOLS), (unsigned)npseg);
-      ozaki_crt_colsq_kernel<<<cgrid, 256, 0, s>>>(cres, n, ncols, oc, rowscale, P);
+      if (prods.sum_in_crt) {
+        const dim3 cgrid((unsigned)((cp + OZ_CRT_BCOLS - 1) / OZ_CRT_BCOLS), (unsigned)npseg);
+        ozaki_crt_colsq_kernel<true><<<cgrid, 256, 0, s>>>(cres, n, ncols, oc, rowscale, P,
+                                                           reinterpret_cast<const uint8_t*>(bres) + prods.p3_off,
+                                                           (int64_t)bplane, prods.p3_blk);
+      } else {
+        const dim3 cgrid((unsigned)((ncols + OZ_CRT_BCOLS - 1) / OZ_CRT_BCOLS), (unsigned)npseg);
+        ozaki_crt_colsq_kernel<false><<<cgrid, 256, 0, s>>>(cres, n, ncols, oc, rowscale, P, nullptr, 0, 0);
+      }
       GP2D_CHECK(check_launch("ozaki_crt_colsq_kernel"));
     }
     GP2D_CHECK(launch_finalize({pm, nmseg, P, npseg, ncols, cp, cv, c0, m, kss, add, clip, compute_var, mean, var,

@@ -546,7 +546,9 @@ __device__ __forceinline__ void vmwait_barrier(std::integral_constant<int, W>) {
 // One launch computes one block product, described by an IgemmProd (below): output row block bi
 // (grid.y, heavy first) and column block blockIdx.x take
 //   C[c_col0 + j][256·bi + r] = (Σ_{t < k_of(bi)/64} A-tile(bi, a_slab0 + t) · B-tile(b_rb0 + bj, b_slab0 + t)
-//                                (+ C[add_col0 + j][256·bi + r])) mod m.
+//                                (+ C[add_col0 + j][256·bi + r])) mod m,
+// where C[col][row] is the byte at c_off + col·ldc + row, or, with c_blk > 0, at
+// c_off + (col / 256)·c_blk + (col % 256)·ldc + row: 256-column blocks c_blk bytes apart.
 // B tiles (256-row layout block rb ≥ alias_rb, k slab s < alias_ks) are read from
 // (rb − alias_rb, s + alias_ks): the four-product K* planes store the (v,u) block only as its
 // equal (u,v) block.  alias_rb = INT_MAX disables the aliasing.
@@ -566,10 +568,12 @@ struct IgemmProd {
   int k_bi0, k_cap;   // k_of(bi) = min(k_cap, 256·(bi − k_bi0 + 1)): A lower-triangular from row block k_bi0
   int c_col0;         // first output column
   int add_col0;       // ≥ 0: the epilogue adds the residues stored at these columns; < 0: none
+  int64_t c_off;      // byte offset of the output's (row 0, column 0) from C
+  int64_t c_blk;      // > 0: bytes between the output's 256-column blocks; 0: 256·ldc (plain column-major)
   // one plain product over whole planes: K columns, lower-triangular A (row block bi needs
   // k < 256·(bi+1)) or dense
   static IgemmProd plain(int K, bool lower) {
-    return {0, 0, INT_MAX, 0, 0, 0, INT_MAX, 0, lower ? 0 : -(1 << 20), K, 0, -1};
+    return {0, 0, INT_MAX, 0, 0, 0, INT_MAX, 0, lower ? 0 : -(1 << 20), K, 0, -1, 0, 0};
   }
 };
 //
@@ -857,11 +861,16 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
   // sum stays in ozaki_mod_u32's range: bias + |Σ| + prior < 2^15·k_cap + 2·256 ≤ 2^15·(2^17 − 256)
   // + 512 < 2^32 for k_cap ≤ n < 131072 (the predict's requirement).
   const OzModConsts mc = ozaki_mod_consts(modulus);
+  // row 0 of output column col, a multiple of TBN: the tile's columns follow ldc apart (IgemmProd)
+  auto cat = [&](int col) -> uint8_t* {
+    const int64_t blk = p.c_blk > 0 ? p.c_blk : IBN * ldc;
+    return C + p.c_off + (col / IBN) * blk + (col % IBN) * ldc;
+  };
   constexpr int NP = (IBM * TBN / 16) / (TBN * 2);   // 16-B runs per thread
   auto epilogue = [&](auto add_c) {
     constexpr bool add = decltype(add_c)::value;
     if constexpr (add) {
-      const uint8_t* Cp = C + (int64_t)(p.add_col0 + j0) * ldc + i0;
+      const uint8_t* Cp = cat(p.add_col0 + j0) + i0;
       i4v pv[NP];
 #pragma unroll
       for (int q = 0; q < NP; ++q) {
@@ -894,7 +903,7 @@ __global__ __launch_bounds__(TBN * 2, (TBN == 256) ? 1 : 2) void igemm_nt_mod_ke
   if (p.add_col0 >= 0) epilogue(std::true_type{});
   else epilogue(std::false_type{});
   __syncthreads();
-  uint8_t* Cc = C + (int64_t)(p.c_col0 + j0) * ldc + i0;
+  uint8_t* Cc = cat(p.c_col0 + j0) + i0;
 #pragma unroll
   for (int q = 0; q < NP; ++q) {
     const int id = tid + TBN * 2 * q;
@@ -1048,15 +1057,54 @@ template <> struct crt_load<8> { typedef uint2 type; };
 #ifndef GP2D_CRT_OCC
 #define GP2D_CRT_OCC 1   // min workgroups (= waves per SIMD) per CU the register budget must allow
 #endif
+// the end of one row's reconstruction: Pint / M from the exact high part and the low part, V_ij
+__device__ __forceinline__ double crt_value(double H, double T, double rs) {
+  const double f = (H - rint(H)) + T;   // Pint / M, centred
+  return f * rs;
+}
+// V_ij² joins the lane's running sum.  |V_ij| ≤ ‖V_j‖₂ ≤ √kss: a value past the limit can only
+// come from a CRT wrap-around (|Pint| ≥ M/2, i.e. too few moduli) — poison the column instead of
+// returning garbage
+__device__ __forceinline__ double crt_square_in(double vij, double vlimit, double acc) {
+  acc = fma(vij, vij, acc);
+  if (fabs(vij) > vlimit) acc = __builtin_nan("");
+  return acc;
+}
+// (r1 + r2) mod m of two residues in [0, m): s − m wraps above s exactly when s < m
+__device__ __forceinline__ uint32_t residue_sum(uint32_t r1, uint32_t r2, uint32_t m) {
+  const uint32_t s = r1 + r2;
+  return min(s, s - m);
+}
+
+// SUM3 = false: one finished residue per output element (the four-product form), as above.
+//
+// SUM3 = true: the three block products of ozaki_host.hpp's OzakiProducts lie side by side and the
+// sum of the residues is taken here.  A modulus's plane of cres holds P2 in the u-out columns and
+// P1 in the v-out columns; P3 (n/2 rows, the v-observation rows, × cp columns) lies outside cres:
+// modulus l's at p3 + l·p3_stride, column j's rows n/2 apart within a 256-column block and the
+// blocks p3_blk bytes apart (the part of the K* planes that nothing reads, OzakiProducts).  The
+// residue of V_u (column j) is P1 ⊕ P2 and that of V_v (column cp + j) is P1 on the u-observation
+// rows and P1 ⊕ P3 on the others, with ⊕ = residue_sum; a wave takes columns j and cp + j together,
+// so P1 is read once.  Two columns at 16 rows per lane would double the H and T registers; instead
+// the wave goes over its segment in passes of 512 rows, 8 rows per lane, and a pair of lanes runs
+// one row chain: lane 2k, then lane 2k + 1 starting from its sum, gives bit for bit what lane k
+// (pass 0) or 32 + k (pass 1) of the other form adds up over its 16 rows.  The passes' sums are added
+// (the other form's first shuffle step) and the remaining shuffle steps run over the odd lanes,
+// so the partial sums P are those of the other form on the summed residues, bit for bit.
+template <bool SUM3>
 __global__ __launch_bounds__(256, GP2D_CRT_OCC) void ozaki_crt_colsq_kernel(const uint8_t* __restrict__ cres, int64_t n,
                                                               int64_t ncols, OzakiConsts oc,
                                                               const double* __restrict__ rowscale,
-                                                              double* __restrict__ P) {
+                                                              double* __restrict__ P,
+                                                              const uint8_t* __restrict__ p3, int64_t p3_stride,
+                                                              int64_t p3_blk) {
   constexpr int RPL = OZ_CRT_RPL;
-  typedef typename crt_load<RPL>::type ld_t;
   const int lane = threadIdx.x & 63;
   const int64_t jw = (int64_t)blockIdx.x * OZ_CRT_BCOLS + (threadIdx.x >> 6) * OZ_CRT_COLS;
   const int64_t seg = blockIdx.y;
+  const int nm1 = oc.nmod - 1;
+  if constexpr (!SUM3) {
+  typedef typename crt_load<RPL>::type ld_t;
   const int64_t i0 = seg * OZ_CRT_ROWS + RPL * lane;
   if (jw >= ncols) return;
   const bool rows_ok = i0 < n;
@@ -1075,7 +1123,6 @@ __global__ __launch_bounds__(256, GP2D_CRT_OCC) void ozaki_crt_colsq_kernel(cons
       for (int c = 0; c < RPL; ++c) { H[c] = 0.0; T[c] = 0.0; }
       // planes in groups of 4 with the group's loads issued together; a group's planes past
       // nmod re-read plane nmod−1 (cached) and add nothing (h = t = 0 beyond nmod)
-      const int nm1 = oc.nmod - 1;
       for (int l0 = 0; l0 < oc.nmod; l0 += 4) {
         ld_t v[4];
 #pragma unroll
@@ -1094,18 +1141,94 @@ __global__ __launch_bounds__(256, GP2D_CRT_OCC) void ozaki_crt_colsq_kernel(cons
         }
       }
 #pragma unroll
-      for (int c = 0; c < RPL; ++c) {
-        const double f = (H[c] - rint(H[c])) + T[c];   // Pint / M, centred
-        const double vij = f * rs[c];
-        acc = fma(vij, vij, acc);
-        // |V_ij| ≤ ‖V_j‖₂ ≤ √kss: a value past the limit can only come from a CRT wrap-around
-        // (|Pint| ≥ M/2, i.e. too few moduli) — poison the column instead of returning garbage
-        if (fabs(vij) > oc.vlimit) acc = __builtin_nan("");
-      }
+      for (int c = 0; c < RPL; ++c) acc = crt_square_in(crt_value(H[c], T[c], rs[c]), oc.vlimit, acc);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     if (lane == 0) P[seg * ncols + j] = acc;
+  }
+  } else {
+  constexpr int HR = 8, NPASS = RPL / HR;   // rows per lane and pass; passes per segment
+  constexpr bool PAIR = NPASS == 2;         // two lanes per 16-row chain
+  const int64_t cp = ncols / 2, npad = n / 2;
+  if (jw >= cp) return;
+  const int64_t plane = n * ncols;
+#pragma unroll 1
+  for (int jc = 0; jc < OZ_CRT_COLS; ++jc) {
+    const int64_t j = jw + jc;
+    if (j >= cp) break;
+    double tot[2] = {0.0, 0.0};   // [V_u, V_v]
+#pragma unroll
+    for (int pass = 0; pass < NPASS; ++pass) {
+      const int64_t i0 = seg * OZ_CRT_ROWS + pass * (64 * HR) + HR * lane;
+      double acc[2] = {0.0, 0.0};
+      if (i0 < n) {   // n is a multiple of 512: a pass has all its rows or none
+        const bool vrow = i0 >= npad;   // a v-observation row (npad is a multiple of 256: all 8 rows or none)
+        double H[2][HR], T[2][HR];
+#pragma unroll
+        for (int c = 0; c < HR; ++c) H[0][c] = H[1][c] = T[0][c] = T[1][c] = 0.0;
+        const uint8_t* c1 = cres + (cp + j) * n + i0;                 // P1
+        const uint8_t* c2 = cres + j * n + i0;                        // P2
+        const uint8_t* c3 = p3 + (j >> 8) * p3_blk + (j & 255) * npad + (i0 - npad);   // P3 (v-observation rows only)
+        // planes in groups of 4, as above, for the three products
+        for (int l0 = 0; l0 < oc.nmod; l0 += 4) {
+          uint2 v1[4], v2[4], v3[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int64_t lu = min(l0 + u, nm1);
+            v1[u] = *reinterpret_cast<const uint2*>(c1 + lu * plane);
+            v2[u] = *reinterpret_cast<const uint2*>(c2 + lu * plane);
+            v3[u] = vrow ? *reinterpret_cast<const uint2*>(c3 + lu * p3_stride) : make_uint2(0u, 0u);   // ⊕ 0 leaves P1
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const uint32_t w1[2] = {v1[u].x, v1[u].y}, w2[2] = {v2[u].x, v2[u].y}, w3[2] = {v3[u].x, v3[u].y};
+            const double h = oc.h[l0 + u], t = oc.t[l0 + u];
+            const uint32_t m = (uint32_t)oc.m[min(l0 + u, nm1)];
+#pragma unroll
+            for (int c = 0; c < HR; ++c) {
+              const int sh = 8 * (c & 3);
+              const uint32_t r1 = (w1[c >> 2] >> sh) & 0xffu, r2 = (w2[c >> 2] >> sh) & 0xffu,
+                             r3 = (w3[c >> 2] >> sh) & 0xffu;
+              const double cu = (double)residue_sum(r1, r2, m), cv = (double)residue_sum(r1, r3, m);
+              H[0][c] = fma(cu, h, H[0][c]);   // exact: multiples of 2^-33 below 2^12
+              T[0][c] = fma(cu, t, T[0][c]);
+              H[1][c] = fma(cv, h, H[1][c]);
+              T[1][c] = fma(cv, t, T[1][c]);
+            }
+          }
+        }
+        double rs[HR];
+#pragma unroll
+        for (int c = 0; c < HR; ++c) rs[c] = rowscale[i0 + c];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          double v[HR];
+#pragma unroll
+          for (int c = 0; c < HR; ++c) v[c] = crt_value(H[e][c], T[e][c], rs[c]);
+          double a = 0.0;
+#pragma unroll
+          for (int c = 0; c < HR; ++c) a = crt_square_in(v[c], oc.vlimit, a);
+          if constexpr (PAIR) {   // the odd lane goes on from the even lane's eight rows
+            a = __shfl(a, lane - 1);
+#pragma unroll
+            for (int c = 0; c < HR; ++c) a = crt_square_in(v[c], oc.vlimit, a);
+          }
+          acc[e] = a;
+        }
+      }
+      // a 16-row chain's sum: in lane 2k + 1 of pass 0 for rows 16k.., of pass 1 for rows 16·(32 + k)..
+      tot[0] = pass == 0 ? acc[0] : tot[0] + acc[0];
+      tot[1] = pass == 0 ? acc[1] : tot[1] + acc[1];
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      double a = tot[e];
+#pragma unroll
+      for (int o = 32; o >= (PAIR ? 2 : 1); o >>= 1) a += __shfl_xor(a, o);
+      if (lane == (PAIR ? 1 : 0)) P[seg * ncols + e * cp + j] = a;
+    }
+  }
   }
 }
 

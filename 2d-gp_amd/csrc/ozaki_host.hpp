@@ -74,14 +74,24 @@ constexpr int64_t oz_s_npad(int64_t n) { return (n > 0 && n % (2 * IBM) == 0) ? 
 //   four products (any n): one launch, V_u = W_L·a + W_R·c and V_v = W_L·c + W_R·b with the (v,u)
 //     block of K* read from its equal (u,v) block c;
 //   three products (oz_s_npad(n) > 0; K* planes hold a − c, c, b − c), S = W_L + W_R:
-//     P1 = S·c → V_v's columns;  P2 = W_L·(a − c), + P1 → V_u;  P3 = W_R·(b − c) on the
-//     v-observation rows (W_R is zero above them), + P1 in place → V_v.  P3 follows P2, which
-//     reads what P3 overwrites.  Residues add mod m, so V's residues are the four-product ones.
+//     P1 = S·c → V_v's columns,  P2 = W_L·(a − c) → V_u's columns,  P3 = W_R·(b − c) on the
+//     v-observation rows (W_R is zero above them).
+//     spare (the K* planes are the workspace's own, gp2d_predict_ozaki): the products are
+//       independent and the CRT pass adds their residues (V_u: P1 + P2; V_v: P1, + P3 on the
+//       v-observation rows; mod m).  P3 goes where the K* planes have room that nothing reads: the
+//       (v,u) block, which is never stored — of layout row block cp/256 + bj the slabs below n/128,
+//       256·n/2 contiguous bytes, exactly P3's column block bj with its columns n/2 apart.  c3 tells
+//       the launch of P3 and the CRT pass where that is (offsets from a modulus's K* plane).
+//     otherwise (planes made ahead belong to the caller and are not written): P2's epilogue adds P1
+//       → V_u; P3 adds P1 in place → V_v, after P2, which reads what P3 overwrites.
+//     Residues add mod m, so either way V's residues are the four-product ones.
 struct OzakiProducts {
   int count;
   IgemmProd prod[3];
   unsigned gx[3], gy[3];
-  OzakiProducts(int64_t n, int64_t cp, bool three) {
+  bool sum_in_crt = false;   // P3 lies in the K* planes and the CRT pass adds the products
+  int64_t p3_off = 0, p3_blk = 0;   // P3's first byte in a modulus's K* plane; bytes between its column blocks
+  OzakiProducts(int64_t n, int64_t cp, bool three, bool spare) {
     const int nb = (int)(n / IBM), nbh = (int)(cp / IBN), hs = (int)(n / 2 / IBK);
     if (!three) {
       count = 1;
@@ -94,10 +104,16 @@ struct OzakiProducts {
     }
     const int nb2 = nb / 2, npad = (int)(n / 2), vcol = (int)cp;
     count = 3;
-    //         bi0  a_slab0 a_fold  a_fold_slab0 b_rb0 b_slab0 alias_rb alias_ks k_bi0 k_cap c_col0 add_col0
-    prod[0] = {0,   0,      nb2,    hs,          0,    hs,     INT_MAX, 0,       0,    npad, vcol,  -1};
-    prod[1] = {0,   0,      INT_MAX, 0,          0,    0,      INT_MAX, 0,       0,    npad, 0,     vcol};
-    prod[2] = {nb2, hs,     INT_MAX, 0,          nbh,  hs,     INT_MAX, 0,       nb2,  npad, vcol,  vcol};
+    sum_in_crt = spare;
+    p3_off = cp * n;             // layout row block cp/256, slab 0
+    p3_blk = (int64_t)IBN * n;   // one layout row block
+    const int add = spare ? -1 : vcol;
+    // P3 among the K* planes: its rows count from the first v-observation row (c_off), leading dimension n/2
+    const int64_t o3 = spare ? -(int64_t)npad : 0, b3 = spare ? p3_blk : 0;
+    //         bi0  a_slab0 a_fold  a_fold_slab0 b_rb0 b_slab0 alias_rb alias_ks k_bi0 k_cap c_col0             add_col0 c_off c_blk
+    prod[0] = {0,   0,      nb2,    hs,          0,    hs,     INT_MAX, 0,       0,    npad, vcol,              -1,      0,    0};
+    prod[1] = {0,   0,      INT_MAX, 0,          0,    0,      INT_MAX, 0,       0,    npad, 0,                 add,     0,    0};
+    prod[2] = {nb2, hs,     INT_MAX, 0,          nbh,  hs,     INT_MAX, 0,       nb2,  npad, spare ? 0 : vcol,  add,     o3,   b3};
     gx[0] = gx[1] = gx[2] = (unsigned)nbh;
     gy[0] = gy[1] = (unsigned)nb;
     gy[2] = (unsigned)nb2;

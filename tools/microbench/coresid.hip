@@ -118,7 +118,7 @@ int main(int argc, char** argv) {
                                                       IgemmProd::plain(n, true), nullptr, nullptr, IgemmZ{});
   };
   auto crt16 = [&](hipStream_t s) {
-    ozaki_crt_colsq_kernel<<<dim3(nc / OZ_CRT_BCOLS, n / OZ_CRT_ROWS), 256, 0, s>>>(dR, n, nc, oc, drs, dP);
+    ozaki_crt_colsq_kernel<false><<<dim3(nc / OZ_CRT_BCOLS, n / OZ_CRT_ROWS), 256, 0, s>>>(dR, n, nc, oc, drs, dP, nullptr, 0, 0);
   };
   auto crt4 = [&](hipStream_t s) { crt4_kernel<<<dim3(nc / C4_BCOLS, n / C4_ROWS), 256, 0, s>>>(dR, n, nc, oc, drs, dP4); };
   hipEvent_t e0, eA, eB;
