@@ -15,6 +15,7 @@
 #include "fields.hpp"
 #include "grad.hpp"
 #include "advect.hpp"
+#include "paths.hpp"
 #include "postcov.hpp"
 #include "predict_host.hpp"
 #include "ozaki.hpp"
@@ -1559,6 +1560,103 @@ int gp2d_advect(const double* alpha, int64_t n, const double* xtr, int64_t ntr, 
                                         fout, m, t0, dt, n0, nst, vel_scale)
                   : launch_advect<false>(tangent != nullptr, grid, s, alpha, xtr, ntr, ntr_pad, ak, at, xin, fin,
                                          xout, fout, m, t0, dt, n0, nst, vel_scale));
+  }
+  return 0;
+}
+
+// ------------------------------------------------- PATHS (ensembles through posterior draws of the flow)
+// what gp2d_paths_eval and gp2d_advect_draws ask of the fit and of the feature table
+static int validate_draws(const char* e, const gp2d_kernel_t* k, int64_t n, int64_t ntr, int64_t ntr_pad,
+                          int64_t nfeat, int ndraws) {
+  const std::string who(e);
+  if (validate_kernel(k) != 0) {
+    set_error(who + ": k is invalid: " + g_err);
+    return -2;
+  }
+  GP2D_REQUIRE(field_kernel_ok(k),
+               who + ": k must be a div-free, curl-free or mixed vector kernel (KIND_SCALAR and the ARD family "
+                     "have no velocity draw)");
+  GP2D_REQUIRE(ntr_pad > 0 && ntr_pad % PT_TILE == 0, who + ": ntr_pad must be a positive multiple of 64");
+  GP2D_REQUIRE(n == 2 * ntr_pad, who + ": n must equal 2 × ntr_pad");
+  GP2D_REQUIRE(ntr > 0 && ntr <= ntr_pad, who + ": ntr must be in 1..ntr_pad");
+  GP2D_REQUIRE(nfeat >= 0 && nfeat < (int64_t)1 << 31, who + ": nfeat must be >= 0 (and below 2^31)");
+  GP2D_REQUIRE(ndraws >= 1, who + ": ndraws must be >= 1");
+  GP2D_REQUIRE(ndraws <= 65535, who + ": ndraws must be <= 65535 (one grid row per draw)");
+  return 0;
+}
+
+int gp2d_paths_eval(const double* alpha, int64_t n, const double* xtr, int64_t ntr, int64_t ntr_pad,
+                    const gp2d_kernel_t* k, const double* feat, int64_t nfeat, int ndraws, const double* xg, int64_t m,
+                    int dim, double t, double* vel, void* stream) {
+  GP2D_REQUIRE((alpha == nullptr) == (k == nullptr),
+               "paths_eval: alpha and k must be both NULL (the feature part alone) or both set");
+  if (k != nullptr) {
+    GP2D_CHECK(validate_draws("paths_eval", k, n, ntr, ntr_pad, nfeat, ndraws));
+    GP2D_REQUIRE(dim == 2, "paths_eval: dim must be 2 with alpha (rows (x1, x2), every point at time t)");
+  } else {
+    GP2D_REQUIRE(nfeat >= 0 && nfeat < (int64_t)1 << 31, "paths_eval: nfeat must be >= 0 (and below 2^31)");
+    GP2D_REQUIRE(ndraws >= 1, "paths_eval: ndraws must be >= 1");
+    GP2D_REQUIRE(ndraws <= 65535, "paths_eval: ndraws must be <= 65535 (one grid row per draw)");
+    GP2D_REQUIRE(dim == 2 || dim == 3, "paths_eval: dim must be 2 (x1, x2) or 3 (t, x1, x2)");
+  }
+  GP2D_REQUIRE(std::isfinite(t), "paths_eval: t must be finite");
+  GP2D_REQUIRE(nfeat == 0 || feat != nullptr, "paths_eval: feat is NULL with nfeat > 0");
+  GP2D_REQUIRE(m >= 0 && m < (int64_t)1 << 36, "paths_eval: m out of range");
+  if (m == 0) return 0;
+  GP2D_REQUIRE(k == nullptr || xtr != nullptr, "paths_eval: xtr is NULL");
+  GP2D_REQUIRE(xg != nullptr, "paths_eval: xg is NULL");
+  GP2D_REQUIRE(vel != nullptr, "paths_eval: vel is NULL");
+  hipStream_t s = S(stream);
+  AdvectKernel ak{};
+  if (k != nullptr) ak = make_advect_kernel(k);
+  const dim3 grid((unsigned)((m + ADV_TILE - 1) / ADV_TILE), (unsigned)ndraws);
+  if (k != nullptr && point_dim(k) == 3)
+    paths_eval_kernel<true><<<grid, ADV_SLICES * ADV_TILE, 0, s>>>(alpha, n, xtr, ntr, ntr_pad, ak, feat, nfeat, xg, m,
+                                                                   dim, t, vel);
+  else
+    paths_eval_kernel<false><<<grid, ADV_SLICES * ADV_TILE, 0, s>>>(alpha, n, xtr, ntr, ntr_pad, ak, feat, nfeat, xg,
+                                                                    m, dim, t, vel);
+  return check_launch("paths_eval_kernel");
+}
+
+int gp2d_advect_draws(const double* alpha, int64_t n, const double* xtr, int64_t ntr, int64_t ntr_pad,
+                      const gp2d_kernel_t* k, const double* feat, int64_t nfeat, int ndraws, const double* x0,
+                      int64_t m, int x0_per_draw, double t0, double dt, int nsteps, int save_every, double vel_scale,
+                      double* path, void* stream) {
+  GP2D_CHECK(validate_draws("advect_draws", k, n, ntr, ntr_pad, nfeat, ndraws));
+  GP2D_REQUIRE(nsteps >= 0, "advect_draws: nsteps must be >= 0");
+  GP2D_REQUIRE(save_every >= 1, "advect_draws: save_every must be >= 1");
+  GP2D_REQUIRE(nsteps == 0 || (std::isfinite(dt) && dt != 0.0), "advect_draws: dt must be finite and non-zero");
+  GP2D_REQUIRE(std::isfinite(t0), "advect_draws: t0 must be finite");
+  GP2D_REQUIRE(std::isfinite(vel_scale), "advect_draws: vel_scale must be finite");
+  GP2D_REQUIRE(x0_per_draw == 0 || x0_per_draw == 1, "advect_draws: x0_per_draw must be 0 or 1");
+  GP2D_REQUIRE(nfeat == 0 || feat != nullptr, "advect_draws: feat is NULL with nfeat > 0");
+  GP2D_REQUIRE(m >= 0 && m < (int64_t)1 << 36, "advect_draws: m out of range");
+  if (m == 0) return 0;
+  GP2D_REQUIRE(alpha != nullptr, "advect_draws: alpha is NULL");
+  GP2D_REQUIRE(xtr != nullptr, "advect_draws: xtr is NULL");
+  GP2D_REQUIRE(x0 != nullptr, "advect_draws: x0 is NULL");
+  GP2D_REQUIRE(path != nullptr, "advect_draws: path is NULL");
+  hipStream_t s = S(stream);
+  const AdvectKernel ak = make_advect_kernel(k);
+  const bool st = point_dim(k) == 3;
+  const int64_t rec = (int64_t)ndraws * m * 2;   // doubles per record
+  paths_init_kernel<<<dim3((unsigned)((m + 255) / 256), (unsigned)ndraws), 256, 0, s>>>(x0, m, x0_per_draw, path);
+  GP2D_CHECK(check_launch("paths_init_kernel"));
+  const dim3 grid((unsigned)((m + ADV_TILE - 1) / ADV_TILE), (unsigned)ndraws);
+  // one launch per saved segment, as in gp2d_advect
+  int64_t r = 0;
+  for (int n0 = 0; n0 < nsteps; n0 += save_every, ++r) {
+    const int nst = std::min(save_every, nsteps - n0);
+    const double* xin = path + r * rec;
+    double* xout = path + (r + 1) * rec;
+    if (st)
+      paths_kernel<true><<<grid, ADV_SLICES * ADV_TILE, 0, s>>>(alpha, n, xtr, ntr, ntr_pad, ak, feat, nfeat, xin, xout,
+                                                                m, t0, dt, n0, nst, vel_scale);
+    else
+      paths_kernel<false><<<grid, ADV_SLICES * ADV_TILE, 0, s>>>(alpha, n, xtr, ntr, ntr_pad, ak, feat, nfeat, xin,
+                                                                 xout, m, t0, dt, n0, nst, vel_scale);
+    GP2D_CHECK(check_launch("paths_kernel"));
   }
   return 0;
 }

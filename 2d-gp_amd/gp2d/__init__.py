@@ -3,6 +3,7 @@
 Layers:
   _native   ctypes binding of libgp2d.so (hand-written HIP for gfx950)
   engine    device-resident fit / predict over the C ABI
+  paths     host side of the posterior flow draws (feature tables, seeded CPU generators)
   kern      the GPy-Kern-style plugin classes (myKernel, nonDivK, nonRotK)
   krig      the reference's krig module surface (Krig, kriging, predict, ...)
   data      index / grid / synthetic-input work (bit-exact with the reference)

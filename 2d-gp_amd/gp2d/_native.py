@@ -54,7 +54,7 @@ EXPORTS = (
     "gp2d_predict_trend_workspace", "gp2d_predict_trend", "gp2d_predict_field_trend",
     "gp2d_lml_trend", "gp2d_lml_grad_trend_workspace", "gp2d_lml_grad_trend",
     "gp2d_loo_grad_workspace", "gp2d_loo_grad",
-    "gp2d_advect_records", "gp2d_advect",
+    "gp2d_advect_records", "gp2d_advect", "gp2d_paths_eval", "gp2d_advect_draws",
 )
 
 
@@ -206,6 +206,8 @@ _SIGS = {
     "gp2d_loo_grad": (_I, [_P, _I64, _I64, _P, _P, _P, _I64, _I64, _KP, _P, _P, _P, _P, _SZ, _P]),
     "gp2d_advect_records": (_I64, [_I, _I]),
     "gp2d_advect": (_I, [_P, _I64, _P, _I64, _I64, _KP, _TP, _P, _P, _I64, _D, _D, _I, _I, _D, _P, _P, _P]),
+    "gp2d_paths_eval": (_I, [_P, _I64, _P, _I64, _I64, _KP, _P, _I64, _I, _P, _I64, _I, _D, _P, _P]),
+    "gp2d_advect_draws": (_I, [_P, _I64, _P, _I64, _I64, _KP, _P, _I64, _I, _P, _I64, _I, _D, _D, _I, _I, _D, _P, _P]),
     "gp2d_gemm": (_I, [_I, _I64, _I64, _I64, _D, _P, _I64, _P, _I64, _D, _P, _I64, _P]),
     "gp2d_transpose": (_I, [_P, _I64, _I64, _P, _P]),
     "gp2d_comm_id_bytes": (_SZ, []),

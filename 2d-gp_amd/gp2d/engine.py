@@ -1377,6 +1377,141 @@ def ftle(tangent, duration: float):
     return torch.log(lam) / (2.0 * abs(float(duration)))
 
 
+@dataclass
+class FlowDraws:
+    """S posterior draws of the flow as functions (draw_flows):
+    g_s(x, t) = f_s(x, t) + K((x, t), X)·α_s, with f_s the draw's random Fourier features."""
+    gp: GPFit
+    alpha: torch.Tensor      # (S, n) device: α_s in the fit's order and padded layout
+    features: torch.Tensor   # (S, F_tot, 6) device: rows [τ, w1, w2, b, a1, a2]
+
+    @property
+    def n_draws(self) -> int:
+        return self.alpha.shape[0]
+
+    def _fit_args(self, desc) -> tuple:
+        gp = self.gp
+        return (_ptr(self.alpha), gp.n, _ptr(gp.x), gp.n_train, gp.n_pad, ctypes.byref(desc),
+                _ptr(self.features), self.features.shape[1], self.n_draws)
+
+    def velocity(self, xg, t: float = 0.0) -> torch.Tensor:
+        """The drawn velocities at the points xg (m, 2) and time t: (S, 2m) on the device, each row
+        [u(g_1..g_m), v(g_1..g_m)] — sample_posterior's layout (gp2d_paths_eval)."""
+        gp = self.gp
+        G = _as_points(xg, 2, gp.device)
+        m = G.shape[0]
+        vel = torch.empty((self.n_draws, 2 * m), dtype=torch.float64, device=gp.device)
+        desc = gp.kernel.desc()
+        N.check(N.lib().gp2d_paths_eval(*self._fit_args(desc), _ptr(G), m, 2, float(t), _ptr(vel),
+                                        _stream_handle(gp.device)), "gp2d_paths_eval")
+        return vel
+
+
+def _draw_matrix(a, shape: tuple, name: str, device) -> torch.Tensor:
+    t = a.to(device=device, dtype=torch.float64) if isinstance(a, torch.Tensor) else \
+        torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float64)), device=device)
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} must have shape {shape}; got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def draw_flows(gp: GPFit, n_draws: int, n_features: int = 1024, seed: int = 0, features=None, eps=None) -> FlowDraws:
+    """n_draws posterior draws of the flow as functions that can be evaluated anywhere — what a
+    moving particle needs (advect_draws).  Pathwise conditioning (Matheron's rule; Wilson et al.
+    2020): g_s = f_s + K(·, X)·α_s with α_s = K_y⁻¹(y − f_s(X) − ε_s), f_s a prior draw of
+    n_features random Fourier features per kernel part (paths.feature_table; every draw has its own,
+    so the ensemble's mean and covariance are exactly the posterior's) and ε_s ~ N(0, (noise +
+    jitter)·I).  Both come from CPU generators seeded with `seed` (the same seed gives the same
+    draws on any machine) or are passed in: features (S, F_tot, 6), eps (S, 2·n_train) in the
+    caller's observation order [u…, v…].
+
+    Builds the table, then the residuals R (S × n, padded rows zero) with f_s(X) from
+    gp2d_paths_eval at the training points in the fit's own order, then α = R·Wᵀ·W as two products
+    on the FP64 GEMM core with the draws as rows (gemm).  A fit of either variance engine serves if
+    it holds W and its observations; an ozaki fit's Morton order is applied to eps.  ValueError,
+    before any device work, for a trend fit (the vague prior on β has no prior draw), a fit without
+    W or without y, the scalar kind and the ARD family."""
+    from . import paths as P
+    if gp.extra.get("trend") is not None:
+        raise ValueError("draw_flows does not support a background flow (trend=): the vague prior on the trend's "
+                         "coefficients has no prior draw")
+    _require_velocity(gp.kernel, "posterior flow draws need a div-free, curl-free or mixed vector kernel "
+                                 "(the scalar kind and the ARD family have no velocity field to follow)")
+    if gp.W is None:
+        raise ValueError("draw_flows needs the fit's factor W = L⁻¹ for K_y⁻¹ = WᵀW (this fit keeps only its int8 "
+                         "planes)")
+    if gp.y is None:
+        raise ValueError("draw_flows needs the fit's observations y (this fit was not made by engine.fit)")
+    S = int(n_draws)
+    if S < 1:
+        raise ValueError("n_draws must be at least 1")
+    ntr, npad, n, dev = gp.n_train, gp.n_pad, gp.n, gp.device
+    if features is None:
+        features = P.feature_table(gp.kernel, S, n_features, seed)
+    elif np.ndim(features) != 3 or np.shape(features)[0] != S or np.shape(features)[2] != P.FEATURE_WIDTH:
+        raise ValueError(f"features must have shape (n_draws, F_tot, {P.FEATURE_WIDTH}); got {tuple(np.shape(features))}")
+    if eps is None:
+        eps = P.noise_draws(S, 2 * ntr, _cv_diag_add(gp), seed)
+    gp.check()
+    feat = _draw_matrix(features, tuple(np.shape(features)), "features", dev)
+    E_ = _draw_matrix(eps, (S, 2 * ntr), "eps", dev).view(S, 2, ntr)
+    if gp.perm is not None:   # sorted point i is input point perm[i]
+        E_ = E_.index_select(2, gp.perm.to(torch.int64))
+    L = N.lib()
+    fX = torch.empty((S, 2, ntr), dtype=torch.float64, device=dev)   # f_s(X), the fit's order
+    N.check(L.gp2d_paths_eval(None, 0, None, 0, 0, None, _ptr(feat), feat.shape[1], S, _ptr(gp.x), ntr,
+                              gp.kernel.input_dim, 0.0, _ptr(fX), _stream_handle(dev)), "gp2d_paths_eval")
+    R = torch.zeros((S, 2, npad), dtype=torch.float64, device=dev)
+    R[:, :, :ntr] = gp.y.view(2, npad)[None, :, :ntr] - fX - E_
+    T = gemm(R.view(S, n), gp.W, transb=True, device=dev)
+    alpha = gemm(T, gp.W, device=dev).contiguous()
+    return FlowDraws(gp=gp, alpha=alpha, features=feat)
+
+
+def advect_draws(draws: FlowDraws, x0, t0: float = 0.0, dt: float = None, nsteps: int = None,
+                 save_every: int | None = None, vel_scale: float = 1.0):
+    """Advect particles through every drawn flow: advect's RK4 of dx/dt = s·g_s(x, t) per draw.
+    x0: (m, 2), one start set shared by the draws, or (S, m, 2), the caller's own uncertainty of the
+    start.  Returns device tensors (times (R,), paths (R, S, m, 2)); the arguments are advect's.
+    One fused kernel per record (gp2d_advect_draws): the update term is advect's training-point sum
+    with the draw's α, the prior term a sum of the same shape over the draw's features.  A (draw,
+    particle)'s results do not depend on the other draws or particles of the call."""
+    if dt is None or nsteps is None:
+        raise ValueError("advect_draws needs dt and nsteps")
+    gp, S = draws.gp, draws.n_draws
+    nsteps = int(nsteps)
+    save_every = max(nsteps, 1) if save_every is None else int(save_every)
+    R = advect_records(nsteps, save_every)
+    per_draw = int(np.ndim(x0) == 3)
+    if per_draw and np.shape(x0)[0] != S:
+        raise ValueError(f"x0 must be (m, 2) or (n_draws, m, 2) with n_draws = {S}; got {tuple(np.shape(x0))}")
+    X0 = _as_points(x0, 2, gp.device)
+    m = X0.shape[0] // S if per_draw else X0.shape[0]
+    path = torch.empty((R, S, m, 2), dtype=torch.float64, device=gp.device)
+    desc = gp.kernel.desc()
+    N.check(N.lib().gp2d_advect_draws(*draws._fit_args(desc), _ptr(X0), m, per_draw, float(t0), float(dt), nsteps,
+                                      save_every, float(vel_scale), _ptr(path), _stream_handle(gp.device)),
+            "gp2d_advect_draws")
+    steps = torch.clamp(torch.arange(R, dtype=torch.float64, device=gp.device) * save_every, max=float(nsteps))
+    return float(t0) + steps * float(dt), path
+
+
+def path_spread(paths):
+    """The ensemble's position statistics per record and particle: (mean (R, m, 2), cov (R, m, 2, 2),
+    count (R, m)) of advect_draws' paths (R, S, m, 2) over the draws — the covariance unbiased
+    (1/(count − 1); NaN where fewer than two draws are left).  A draw whose position is NaN (a
+    non-finite start) is left out and count says how many were kept.  Pure torch, on any device."""
+    P_ = torch.as_tensor(paths)
+    ok = torch.isfinite(P_).all(-1)                        # (R, S, m)
+    cnt = ok.sum(1)                                        # (R, m)
+    z = torch.where(ok[..., None], P_, torch.zeros_like(P_))
+    mean = z.sum(1) / cnt[..., None]
+    d = torch.where(ok[..., None], P_ - mean[:, None], torch.zeros_like(P_))
+    cov = torch.einsum("rsma,rsmb->rmab", d, d) / (cnt - 1).clamp(min=0)[..., None, None]
+    cov = torch.where((cnt > 1)[..., None, None], cov, torch.full_like(cov, float("nan")))
+    return mean, cov, cnt
+
+
 def _predict_cov_padded(gp: GPFit, xg, diag_add: float):
     """gp2d_predict_cov: (mean (2m,), the padded q × q covariance, m, mp) on the device."""
     _refuse_sum(gp.kernel, "predict_cov")

@@ -252,6 +252,26 @@ class Krig:
                              vel_scale=vel_scale, tangent=True)
         return _to_numpy(E.ftle(tan[-1], duration)).reshape([np.size(y), -1])
 
+    # ------------------------------------------------------------------ path uncertainty
+    def draw_flows(self, n_draws: int, n_features: int = 1024, seed: int = 0):
+        """n_draws posterior draws of the flow as functions (engine.draw_flows): an engine.FlowDraws,
+        whose velocity(Xg, t) gives the draws at any points and which engine.advect_draws integrates."""
+        self._check()
+        return E.draw_flows(self.gp, n_draws, n_features=n_features, seed=seed)
+
+    def advect_ensemble(self, X0, n_draws: int, t0: float = 0.0, dt: float = None, nsteps: int = None,
+                        save_every: int | None = None, vel_scale: float = 1.0, n_features: int = 1024, seed: int = 0):
+        """Where a parcel could be, and how sure we are: particles released at X0 ((M, 2), or
+        (n_draws, M, 2) for an uncertain release) advected through n_draws posterior draws of the flow.
+        Returns numpy arrays (times (R,), paths (R, S, M, 2), mean (R, M, 2), cov (R, M, 2, 2), count
+        (R, M)) — the trajectories of every draw and engine.path_spread of them: the ensemble mean
+        position (not the path through the mean flow, which Krig.advect gives), its 2 × 2 covariance
+        and the number of draws behind them.  The other arguments are advect's."""
+        draws = self.draw_flows(n_draws, n_features=n_features, seed=seed)
+        t, paths = E.advect_draws(draws, X0, t0=t0, dt=dt, nsteps=nsteps, save_every=save_every, vel_scale=vel_scale)
+        mean, cov, cnt = E.path_spread(paths)
+        return _to_numpy(t), _to_numpy(paths), _to_numpy(mean), _to_numpy(cov), _to_numpy(cnt)
+
     # ------------------------------------------------------------------ joint covariance, samples
     def predict_cov(self, Xg):
         """(mean (2M, 1), cov (2M, 2M)) numpy arrays: the posterior mean and the full latent

@@ -661,6 +661,49 @@ int gp2d_advect(const double* alpha, int64_t n, const double* xtr, int64_t ntr, 
                 const double* x0, int64_t m, double t0, double dt, int nsteps, int save_every, double vel_scale,
                 double* path, double* tangent, void* stream);
 
+/* ---- ensembles advected through posterior draws of the flow: path uncertainty (DESIGN.md §3.14;
+ * added within ABI 11) ----
+ * Pathwise conditioning (Matheron's rule; Wilson et al. 2020) writes a posterior draw as a function
+ * that can be evaluated anywhere:
+ *     g_s(x, t) = f_s(x, t) + K((x, t), X)·α_s,   α_s = K_y⁻¹(y − f_s(X) − ε_s),
+ * f_s a prior draw held as a finite sum of random Fourier features,
+ *     f_s(x, t) = Σ_j (a1_j, a2_j)·sin(w1_j·x1 + w2_j·x2 + τ_j·t + b_j),
+ * and ε_s ~ N(0, (noise + jitter)·I).  The caller owns the randomness and the solve: feat
+ * (ndraws × nfeat × 6 doubles, rows [τ, w1, w2, b, a1, a2], kind, ratio, sum weights and var_t
+ * folded into (a1, a2); every draw has its own rows) and alpha (ndraws × n, row s = α_s in
+ * gp2d_advect's layout, n = 2·ntr_pad) are inputs.  Replaces nothing in the reference, which never
+ * draws from its posterior.  No workspace, no atomics, fixed summation order; a workgroup is 64
+ * points of one draw.  Kernels as for gp2d_advect: VECTOR2D, VECTOR_ST and VECTOR_SUM of kinds
+ * DIVFREE, CURLFREE or MIXED; KIND_SCALAR and the ARD family are refused.
+ * gp2d_paths_eval: vel (ndraws × 2m doubles, [s][u_1..u_m, v_1..v_m]) = g_s at the m points xg
+ *   (rows of dim doubles).  With alpha and k: dim = 2, rows (x1, x2), every point at time t (the
+ *   purely spatial families ignore t in the update term; τ·t is always added to the phase).  alpha =
+ *   NULL and k = NULL (both or neither): the feature part f_s alone — how f_s(X) of the residual is
+ *   formed —, n, xtr, ntr, ntr_pad unused, and dim = 3 is allowed: rows (t_j, x1, x2), each point at
+ *   its own time (t unused).  nfeat = 0 with alpha: the update term alone (K·α_s).
+ * gp2d_advect_draws: gp2d_advect's RK4 (no tangent) of dx/dt = vel_scale·g_s(x, t) for every draw.
+ *   x0_per_draw = 0: one m × 2 start set shared by every draw; 1: ndraws × m × 2, the caller's
+ *   uncertainty of the start.  path (R·ndraws·m·2 doubles, [r][s][j][2], R =
+ *   gp2d_advect_records(nsteps, save_every)): record 0 the starts, record r the positions after step
+ *   min(r·save_every, nsteps).  One launch per record; the state passes through memory in FP64 and
+ *   step n starts at t0 + n·dt, so the results do not depend on save_every.  The results of a
+ *   (draw, particle) do not depend on m, ndraws, the particle's index or the draw's index: a caller
+ *   may shard draws and particles freely.  A non-finite start gives NaN in every record of that
+ *   (draw, particle) and touches nothing else.  nsteps = 0 writes record 0 only; m = 0 returns 0
+ *   without a launch.
+ * Checked on the host before any device work, each naming its parameter: gp2d_advect's checks (k's
+ *   family and kind, n == 2·ntr_pad, 0 < ntr ≤ ntr_pad, nsteps ≥ 0, save_every ≥ 1, dt finite and
+ *   non-zero when nsteps > 0, t0, t and vel_scale finite, the pointers not NULL when m > 0), and
+ *   nfeat ≥ 0, 1 ≤ ndraws ≤ 65535 (a grid row per draw), feat not NULL when nfeat > 0, x0_per_draw 0
+ *   or 1, dim 2 or 3 as above.                                                                   */
+int gp2d_paths_eval(const double* alpha, int64_t n, const double* xtr, int64_t ntr, int64_t ntr_pad,
+                    const gp2d_kernel_t* k, const double* feat, int64_t nfeat, int ndraws,
+                    const double* xg, int64_t m, int dim, double t, double* vel, void* stream);
+int gp2d_advect_draws(const double* alpha, int64_t n, const double* xtr, int64_t ntr, int64_t ntr_pad,
+                      const gp2d_kernel_t* k, const double* feat, int64_t nfeat, int ndraws,
+                      const double* x0, int64_t m, int x0_per_draw, double t0, double dt, int nsteps,
+                      int save_every, double vel_scale, double* path, void* stream);
+
 /* ---- dense helpers (the GP_scripts functional API on explicit matrices) ------------
  * gp2d_gemm: C = alpha·A·op(B) + beta·C on the FP64 MFMA GEMM core; op(B) = B (transb = 0,
  *   B is k×n) or Bᵀ (transb = 1, B is n×k); row-major; m, n multiples of 128, k of 16 (the
